@@ -13,7 +13,14 @@ Other configs: --config c1 (one N=1024 fft_exec on HOST buffers: latency, next t
 reference timed in the same run), c3 (12600 x 65536), c4 (Bluestein 99991 x 8192), c5 (r2c
 2^22 x 32768 over the job, chunked per GPU).
 
-roofline: achieved = algorithmic bytes of the whole step (32 B per complex
+A plain run does only what the headline figure needs: it sets up, warms up, times --steps steps
+between synchronising barriers, writes its outputs if --dump-outputs is given and prints the
+result line (`ms_per_step` is the wall time of one timed step).  Everything else -- the
+event-timed re-run with its roofline and per-launch figures, the stream-copy ceiling, the
+placement probe, the reference timed on the host cores and the other BASELINE configs after a
+one-rank c2 run -- is measured only with --full.
+
+roofline (--full): achieved = algorithmic bytes of the whole step (32 B per complex
 sample for c2c) / the event-timed step time, i.e. the transform as a whole, every launch of
 the step included; `pass_frac` lists the same figure per launch of a multi-launch step.
 """
@@ -40,6 +47,49 @@ CONFIGS = {
     "c4": ("c2c", 99991, 8192, 0x5EED0004, "Bluestein c2c N=99991, batch=8192 per GPU, fp64"),
     "c5": ("r2c", 1 << 22, 4096, 0x5EED0005, "r2c N=2^22, 4096 rows per GPU (32768 over 8 GPUs), fp64"),
 }
+
+
+DUMP_SAMPLE_BYTES = 32 << 20  # --dump-outputs: the sample of an output too large to write whole
+
+
+def sample_indices(total, k, seed):
+    """at most k distinct indices of range(total), sorted, the first and the last among them;
+    the others are a fixed function of `seed`, the same from run to run"""
+    import numpy as np
+    if total <= k:
+        return np.arange(total, dtype=np.int64)
+    idx = np.unique((seed % total + np.arange(k, dtype=np.int64) * 2654435761) % total)
+    idx[0] = 0
+    if len(idx) > 1:
+        idx[-1] = total - 1
+    return idx
+
+
+def dump_name(ws, rank):
+    """one rank writes output.npy; every rank of several its own output_rank<r>.npy"""
+    return "output" if ws == 1 else f"output_rank{rank}"
+
+
+def dump_outputs(dirpath, name, fetch_row, rows, rowlen, seed):
+    """--dump-outputs: what the timed path left for its caller, a (rows, rowlen) array, written as
+    float64 to DIR/<name>.npy (a complex row as (re, im) pairs in a trailing axis of 2).  An
+    output of more than DUMP_SAMPLE_BYTES is sampled: up to 65536 columns of as many rows as fit,
+    chosen by sample_indices (the same for the same arguments); their indices go to
+    <name>_rows.npy and <name>_cols.npy.  `fetch_row(r)` returns row r as a host array."""
+    import numpy as np
+    first = np.asarray(fetch_row(0))
+    per = 16 if np.iscomplexobj(first) else 8
+    cols = sample_indices(rowlen, 65536 if rows * rowlen * per > DUMP_SAMPLE_BYTES else rowlen, seed)
+    pick = sample_indices(rows, max(1, DUMP_SAMPLE_BYTES // (len(cols) * per)), seed >> 7)
+    out = np.empty((len(pick), len(cols)), dtype=first.dtype)
+    for i, r in enumerate(pick):
+        out[i] = (first if r == 0 else np.asarray(fetch_row(int(r))))[cols]
+    if np.iscomplexobj(out):
+        out = np.ascontiguousarray(out.astype(np.complex128)).view(np.float64).reshape(len(pick), len(cols), 2)
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, name + ".npy"), out.astype(np.float64, copy=False))
+    np.save(os.path.join(dirpath, name + "_rows.npy"), pick.astype(np.float64))
+    np.save(os.path.join(dirpath, name + "_cols.npy"), cols.astype(np.float64))
 
 
 def dist_env():
@@ -157,6 +207,8 @@ def dry_run(args, comm, ws, rank):
     rows = comm.gather(r0)
     checks = comm.gather(float(np.abs(y).sum()))
     lib.orc_plan_destroy(p)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dump_name(ws, rank), lambda r: y[r], batch, n, 0x5EED0002)
     ms = wall / args.steps * 1e3
     # the same per-rank / aggregate fields as a GPU line (the CPU "event" time is the wall time)
     per, agg = rank_fields(comm, ws, local, args.steps, local / args.steps * 1e3, n * batch * 32)
@@ -167,7 +219,7 @@ def dry_run(args, comm, ws, rank):
             "dry_run": True, "per_rank_batch": batch, "row_starts": [int(r) for r in rows],
             "rank_checksums": checks, "per_rank": per,
             "roofline": {"bound": "hbm", "unit": "GB/s", "aggregate": agg}}
-        if not args.no_cpu_baseline:  # rank 0, after the timed region, as on the GPU line
+        if args.full and not args.no_cpu_baseline:  # rank 0, after the timed region, as on the GPU line
             out["cpu_baseline"] = cpu_baseline(("c2c", n, batch, 0x5EED0002, ""), seconds_target=0.5)
         print(json.dumps(out), flush=True)
 
@@ -318,7 +370,9 @@ def bench_c1(args, comm, ws, rank):
                           "mean": round(us[3], 2)},
            "latency_us_ctypes": {"p10": round(lat[len(lat) // 10] * 1e6, 2), "median": round(lat[len(lat) // 2] * 1e6, 2),
                                  "p90": round(lat[len(lat) * 9 // 10] * 1e6, 2)}}
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dump_name(ws, rank), lambda r: y, 1, n, seed)
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cb = c1_cpu_baseline(seed)
         if cb:
             out["cpu_baseline"] = cb
@@ -603,6 +657,10 @@ def bench_convolve(args, comm, ws, rank):
     comm.barrier()
     wall = comm.max(time.perf_counter() - t0)
     ms = wall / args.steps * 1e3
+    if args.dump_outputs:
+        import numpy as np
+        dump_outputs(args.dump_outputs, dump_name(ws, rank),
+                     lambda r: dout.to_array(np.float64, clen, r * clen * 8), rows, clen, 0x5EED0006)
     if rank == 0:
         print(json.dumps({"metric": "GSamples/s (batched linear convolution, padded length P x rows per second)",
                           "value": round(rows * P * ws / (ms / 1e3) / 1e9, 3), "unit": "GSamples/s", "n_gpus": ws,
@@ -624,11 +682,21 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="override per-GPU batch (development only)")
     ap.add_argument("--n", type=int, default=0, help="override the transform length (development only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the event-timed "
+                         "re-run (event_ms_per_step, roofline, per-launch and per-rank figures), the stream-copy "
+                         "ceiling, the placement probe, the reference on the host cores (cpu_baseline) and, after "
+                         "a one-rank c2 run, BASELINE configs c1, c3, c4, c5 (other_configs)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/output.npy "
+                         "(several ranks: output_rank<r>.npy) as float64, complex values as (re, im) pairs; an "
+                         "output over 32 MiB as a fixed sample of rows and columns whose indices are written "
+                         "beside it (output_rows.npy, output_cols.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="wall-time target of the cpu_baseline leg's timed sweeps (tests shorten it)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="c2, one rank: skip timing BASELINE configs c1, c3, c4, c5 after the headline")
+                    help="--full, c2, one rank: skip timing BASELINE configs c1, c3, c4, c5 after the headline")
     ap.add_argument("--r2c-compact", action="store_true",
                     help="c5 only: hsfft_r2c_batched_compact (N/2+1 bins per row) instead of the reference layout")
     ap.add_argument("--c2r", action="store_true",
@@ -651,6 +719,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))  # before any GPU call in this process
     ws, rank, local = dist_env()
@@ -766,29 +836,75 @@ def bench_main(args, comm, ws, rank, local):
         return comm.max(local), local
 
     # the buffers as first allocated -- what a caller's plain hipMalloc gets; no placement
-    # selection (probe_placement only reports the output buffer's slice copy rates)
+    # selection (--full: probe_placement only reports the output buffer's slice copy rates)
     if fill is not None:
-        place = probe_placement(din, dout)
+        if args.full:
+            place = probe_placement(din, dout)
         fill()
         hsfft.synchronize()
     wall, wall_local = timed_steps()
+    npass = plan.num_passes() if kind == "c2c" else 0
 
-    # HIP-event timing on the library stream (what the kernels take) + per-pass breakdown
-    npass = 0
-    pass_ms = []
-    if kind == "c2c":
-        ev_ms, pms = hsfft.time_batched(plan, din, dout, batch, max(1, args.steps))
-        npass = plan.num_passes()
-        pass_ms = [p for p in pms[:npass] if p > 0]
-    elif args.r2c_compact or args.c2r:
-        ev_ms = wall * 1e3
-    else:
-        ev_ms = hsfft.time_r2c_batched(plan, din, dout, chunk, max(1, args.steps)) * (batch / chunk)
-    ev_local_ms = ev_ms / max(1, args.steps)
-    ev_step_ms = comm.max(ev_local_ms)
+    # what the last timed step left for its caller (before anything below overwrites dout)
+    if args.dump_outputs:
+        import numpy as np
+        if kind == "c2c":
+            orows, olen, odt = batch, n, np.complex128
+        elif args.c2r:
+            orows, olen, odt = batch, n, np.float64
+        else:  # r2c: the output buffer holds the step's last chunk of rows
+            orows = batch - (batch - 1) // chunk * chunk
+            olen, odt = (n // 2 + 1) if args.r2c_compact else n, np.complex128
+        osz = np.dtype(odt).itemsize
+        dump_outputs(args.dump_outputs, dump_name(ws, rank),
+                     lambda r: dout.to_array(odt, olen, r * olen * osz), orows, olen, seed)
 
     ms_per_step = wall / args.steps * 1e3
     value = samples * ws / (ms_per_step / 1e3) / 1e9
+
+    def full_fields(out):
+        """--full: the steps again between HIP events on the library stream (what the kernels
+        take) with the per-pass breakdown, the roofline figures from it, and a stream copy of the
+        same buffers, which overwrites dout"""
+        pass_ms = []
+        if kind == "c2c":
+            ev_ms, pms = hsfft.time_batched(plan, din, dout, batch, args.steps)
+            pass_ms = [p for p in pms[:npass] if p > 0]
+        elif args.r2c_compact or args.c2r:
+            ev_ms = wall * 1e3
+        else:
+            ev_ms = hsfft.time_r2c_batched(plan, din, dout, chunk, args.steps) * (batch / chunk)
+        ev_local_ms = ev_ms / args.steps
+        ev_step_ms = comm.max(ev_local_ms)
+        out["event_ms_per_step"] = round(ev_step_ms, 4)
+        if place:
+            out["placement"] = place
+        # the transform as a whole: algorithmic bytes of the step / event-timed step time
+        ach = samples * bytes_per_sample / (ev_step_ms / 1e3) / 1e9
+        ent = traffic_entry(args.config)
+        kern = ent.get("kernel", "").replace("void ", "") if ent.get("batch") == batch else ""
+        launches = f"{max(npass, 1)} launch(es)"
+        if kind == "c2c" and plan.header()["lt"] != 0 or args.config == "c4":  # Bluestein
+            launches = ("one persistent launch (bxc::k_bxcd) per 65536 rows"
+                        if os.environ.get("HSFFT_BLUE_XCD", "8") != "0" else "3 launches per 1024-row chunk")
+        out["roofline"] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": read_traffic(args.config, batch),
+                           "algorithmic_bytes": samples * bytes_per_sample,
+                           "basis": f"whole step: {bytes_per_sample} B x N x batch / event-timed step time, "
+                                    f"{launches} of the step",
+                           "kernel": kern or f"{launches} per step"}
+        if ws > 1:  # every rank's own numbers, and the whole job's bytes against ws x the peak
+            out["per_rank"], out["roofline"]["aggregate"] = rank_fields(comm, ws, wall_local, args.steps,
+                                                                        ev_local_ms, samples * bytes_per_sample)
+        if pass_ms:
+            out["roofline"]["pass_ms"] = [round(p, 4) for p in pass_ms]
+            out["roofline"]["pass_frac"] = [round(samples * bytes_per_sample / (p / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
+                                            for p in pass_ms]
+        # practical HBM ceiling of the device: a 16-B-per-lane stream copy of the same buffers
+        nbytes = min(din.nbytes, dout.nbytes) // 16 * 16
+        cms = hsfft.bench_copy(din, dout, nbytes, 5)
+        out["stream_copy_gbs"] = round(2 * nbytes * 5 / (cms / 1e3) / 1e9, 1)
+
     out = {
         "metric": "GSamples/s + achieved HBM GB/s, batched 1D c2c FFT N=2^20 at 1/2/4/8 MI355X"
         if args.config == "c2" else f"GSamples/s ({desc})",
@@ -807,33 +923,8 @@ def bench_main(args, comm, ws, rank, local):
                    "parallelism": f"batch-sharded x{ws} (no collective)", "passes": npass,
                    **({"output_chunk_rows": chunk} if chunk != batch else {})},
         "achieved_hbm_gbs": round(samples * bytes_per_sample * ws / (ms_per_step / 1e3) / 1e9, 1),
-        "event_ms_per_step": round(ev_step_ms, 4),
     }
-    if place:
-        out["placement"] = place
     out["value_basis"] = "buffers as first allocated (plain hipMalloc, no placement selection)"
-    # the transform as a whole: algorithmic bytes of the step / event-timed step time
-    ach = samples * bytes_per_sample / (ev_step_ms / 1e3) / 1e9
-    ent = traffic_entry(args.config)
-    kern = ent.get("kernel", "").replace("void ", "") if ent.get("batch") == batch else ""
-    launches = f"{max(npass, 1)} launch(es)"
-    if kind == "c2c" and plan.header()["lt"] != 0 or args.config == "c4":  # Bluestein
-        launches = ("one persistent launch (bxc::k_bxcd) per 65536 rows"
-                    if os.environ.get("HSFFT_BLUE_XCD", "8") != "0" else "3 launches per 1024-row chunk")
-    out["roofline"] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                       "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": read_traffic(args.config, batch),
-                       "algorithmic_bytes": samples * bytes_per_sample,
-                       "basis": f"whole step: {bytes_per_sample} B x N x batch / event-timed step time, "
-                                f"{launches} of the step",
-                       "kernel": kern or f"{launches} per step"}
-    if ws > 1:  # every rank's own numbers, and the whole job's bytes against ws x the peak
-        out["per_rank"], out["roofline"]["aggregate"] = rank_fields(comm, ws, wall_local, args.steps, ev_local_ms,
-                                                                    samples * bytes_per_sample)
-    if pass_ms:
-        out["roofline"]["pass_ms"] = [round(p, 4) for p in pass_ms]
-        out["roofline"]["pass_frac"] = [round(samples * bytes_per_sample / (p / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
-                                        for p in pass_ms]
-    # (before the copy benchmark below overwrites dout)
     if args.dump_rows and not args.c2r:
         import numpy as np
         g0 = row_range(rank, batch)[0]
@@ -848,10 +939,8 @@ def bench_main(args, comm, ws, rank, local):
         os.makedirs(args.dump_rows, exist_ok=True)
         np.savez(os.path.join(args.dump_rows, f"rank{rank}.npz"), rows=rows,
                  global_rows=np.array([g0 + r for r in picks]), n=n, seed=seed, world=ws, kind=kind)
-    # practical HBM ceiling on this device: a 16-B-per-lane stream copy of the same buffers
-    nbytes = min(din.nbytes, dout.nbytes) // 16 * 16
-    cms = hsfft.bench_copy(din, dout, nbytes, 5)
-    out["stream_copy_gbs"] = round(2 * nbytes * 5 / (cms / 1e3) / 1e9, 1)
+    if args.full:
+        full_fields(out)
     if args.host_rows and kind == "c2c":
         import numpy as np
         hb = min(args.host_rows, batch)
@@ -865,11 +954,12 @@ def bench_main(args, comm, ws, rank, local):
                                 "pcie_gbs": round(2 * hx.nbytes / hs / 1e9, 1),
                                 "note": "host (pageable numpy) rows in and out, upload/transform/download overlapped; "
                                         "PCIe-inclusive, not the headline value"}
-    if rank == 0 and not args.no_cpu_baseline and not args.c2r:
-        # rank 0, after every rank's timed region (at N > 1 too: north_star wants the reference
-        # timed on the host cores in the same run next to the 1/2/4/8-GPU numbers)
+    if args.full and rank == 0 and not args.no_cpu_baseline and not args.c2r:
+        # rank 0, after every rank's timed region (at N > 1 too: the reference is timed on the
+        # host cores in the same run next to the 1/2/4/8-GPU numbers)
         out["cpu_baseline"] = cpu_baseline(cfg, seconds_target=args.cpu_seconds)
-    if ws == 1 and args.config == "c2" and not args.batch and not args.n and not args.no_other_configs:
+    if (args.full and ws == 1 and args.config == "c2" and not args.batch and not args.n
+            and not args.no_other_configs):
         din.free()
         dout.free()
         out["other_configs"] = other_configs(cpu=not args.no_cpu_baseline)

@@ -29,7 +29,7 @@ def run_two_ranks(tmp_path, config, batch, cpu=False, ranks=2):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(T.REPO, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
-           "--config", config, "--batch", str(batch), "--dump-rows", str(out)]
+           "--full", "--config", config, "--batch", str(batch), "--dump-rows", str(out)]
     cmd += ["--cpu-seconds", "1"] if cpu else ["--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400, cwd=T.REPO)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -95,6 +95,39 @@ def test_four_ranks_shard_rows_bit_exact(tmp_path):
     assert seen == {0, 2, 3, 5, 6, 8, 9, 11}
 
 
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """a plain run (no --full) prints the headline fields and none of the extra measurements;
+    --dump-outputs writes the last timed step's output -- here 4 rows of 2^20, 64 MiB, so a
+    sample of 65536 columns of every row -- as float64 (re, im) pairs, bit-exact against the
+    oracle's transform of the same seeded rows"""
+    if hsfft.device_count() < 1:
+        pytest.skip("no GPU")
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(T.REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", "4", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=T.REPO)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "GSamples/s" and d["higher_is_better"] is True and d["dtype"] == "f64 (complex128)"
+    # both figures are rounded in the line (ms_per_step to 1e-4 ms of a step of at least 0.02 ms)
+    assert d["value"] == pytest.approx(4 * (1 << 20) / (d["ms_per_step"] / 1e3) / 1e9, rel=5e-3)
+    for k in ("roofline", "cpu_baseline", "other_configs", "stream_copy_gbs", "placement", "event_ms_per_step"):
+        assert k not in d, k
+    got = np.load(out / "output.npy")
+    rows, cols = (np.load(out / f"output_{w}.npy").astype(np.int64) for w in ("rows", "cols"))
+    assert got.dtype == np.float64 and got.shape == (4, 65536, 2) and rows.tolist() == [0, 1, 2, 3]
+    assert cols[0] == 0 and cols[-1] == (1 << 20) - 1 and np.all(np.diff(cols) > 0)
+    x = T.complex_input(1 << 20, T.SEEDS[2], batch=4).reshape(4, 1 << 20)
+    ref = np.ascontiguousarray(T.oracle_c2c(x, 1)[:, cols])
+    assert T.bits_equal(got.reshape(4, 2 * 65536).view(np.complex128), ref)
+
+
 def test_one_gpu_line_contract(tmp_path):
     """the N = 1 bench line carries the contract's fields: metric / value / unit / n_gpus /
     steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data /
@@ -106,7 +139,7 @@ def test_one_gpu_line_contract(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(T.REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--config", "c2",
-           "--batch", "4", "--no-other-configs", "--cpu-seconds", "0.5"]
+           "--full", "--batch", "4", "--no-other-configs", "--cpu-seconds", "0.5"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=T.REPO)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

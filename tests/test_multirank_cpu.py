@@ -22,14 +22,14 @@ def free_port():
         return s.getsockname()[1]
 
 
-def run_bench(nproc, batch, n, launcher=True):
+def run_bench(nproc, batch, n, launcher=True, extra=("--full",)):
     """launcher: under torch.distributed.run (how the driver starts N ranks); else plain
     `bench.py --gpus N`, which starts its N rank processes itself"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     args = [os.path.join(REPO, "bench.py"), "--gpus", str(nproc), "--dry-run", "--steps", "2", "--warmup", "1",
-            "--batch", str(batch), "--dry-n", str(n)]
+            "--batch", str(batch), "--dry-n", str(n), *extra]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr=127.0.0.1", f"--master-port={free_port()}"] + args if launcher else [sys.executable] + args
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
@@ -65,6 +65,46 @@ def test_bench_multirank_dry_run(nproc, launcher):
     assert agg["frac"] == pytest.approx(agg["achieved"] / agg["peak"], abs=1e-4)
     cb = out["cpu_baseline"]
     assert cb["value"] > 0 and cb["cores"] >= 1 and cb["kind"] in ("reference", "port") and cb["unit"] == "GSamples/s"
+
+
+def test_plain_dry_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """without --full the line keeps the headline fields and times no cpu_baseline; --dump-outputs
+    writes the last step's rows as float64 (re, im) pairs, equal to the oracle's transform of the
+    same seeded rows, and the same bytes from run to run"""
+    n, batch = 256, 3
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        out = run_bench(1, batch, n, launcher=False, extra=("--dump-outputs", str(d)))
+        assert "cpu_baseline" not in out
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["unit"] == "GSamples/s" and out["higher_is_better"] is True and out["metric"]
+    a, b = (np.load(d / "output.npy") for d in dirs)
+    assert a.dtype == np.float64 and a.shape == (batch, n, 2) and T.bits_equal(a, b)
+    assert np.load(dirs[0] / "output_rows.npy").tolist() == [0, 1, 2]
+    assert np.load(dirs[0] / "output_cols.npy").tolist() == list(range(n))
+    x = T.complex_input(n, 0x5EED0002, batch=batch).reshape(batch, n)
+    assert T.bits_equal(a.reshape(batch, 2 * n).view(np.complex128), T.oracle_c2c(x, 1))
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """an output over the sample size is written as a fixed choice of rows and columns (first and
+    last included, sorted, distinct) that stays under 64 MB"""
+    sys.path.insert(0, REPO)
+    import bench
+    import tempfile
+    rows, n = 40, 1 << 17   # 40 x 2^17 complex128 = 80 MiB
+    cols = bench.sample_indices(n, 65536, 0x5EED0002)
+    assert len(cols) == 65536 and cols[0] == 0 and cols[-1] == n - 1 and np.all(np.diff(cols) > 0)
+    assert np.array_equal(cols, bench.sample_indices(n, 65536, 0x5EED0002))
+    row = lambda r: (np.arange(n) + 1j * r).astype(np.complex128)  # noqa: E731
+    with tempfile.TemporaryDirectory() as d:
+        bench.dump_outputs(d, "output", row, rows, n, 0x5EED0002)
+        got, pick = np.load(os.path.join(d, "output.npy")), np.load(os.path.join(d, "output_rows.npy")).astype(int)
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 * 10**6
+    assert got.dtype == np.float64 and got.shape == (len(pick), 65536, 2) and len(pick) == 32
+    assert pick[0] == 0 and pick[-1] == rows - 1 and np.all(np.diff(pick) > 0)
+    assert np.array_equal(got[:, :, 0], np.broadcast_to(cols, (32, 65536)))
+    assert np.array_equal(got[:, :, 1], np.broadcast_to(pick[:, None], (32, 65536)))
 
 
 def test_row_range_partition():

@@ -1,12 +1,13 @@
 #!/bin/bash
-# full GPU suite, then the default bench exactly as the driver runs it (all configs + CPU baseline)
+# full GPU suite, then the benchmark with everything it measures (--full: all configs + CPU baseline)
+# logs go to $OUT (default bench_out/ in the repository root)
 set -u
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export TMPDIR=/tmp
-timeout -k 10 1000 python -u -m pytest tests -m gpu -v -x --timeout 300 --timeout-method thread -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1
-rc=$?; echo "pytest rc=$rc"; tail -3 gpurun_out/pytest_gpu.log
+cd "$(dirname "$0")/.."; OUT=${OUT:-bench_out}; mkdir -p "$OUT"; export TMPDIR=/tmp
+timeout -k 10 1000 python -u -m pytest tests -m gpu -v -x --timeout 300 --timeout-method thread -p no:cacheprovider > "$OUT"/pytest_gpu.log 2>&1
+rc=$?; echo "pytest rc=$rc"; tail -3 "$OUT"/pytest_gpu.log
 case $rc in 0) ;; *) exit $rc;; esac
-timeout -k 10 600 python bench.py > gpurun_out/bench_default.log 2>&1; rc=$?; echo "bench rc=$rc"
-grep '^{' gpurun_out/bench_default.log | python3 -c "
+timeout -k 10 600 python bench.py --full > "$OUT"/bench_default.log 2>&1; rc=$?; echo "bench rc=$rc"
+grep '^{' "$OUT"/bench_default.log | python3 -c "
 import json,sys
 for l in sys.stdin:
     d=json.loads(l); r=d['roofline']
