@@ -194,8 +194,8 @@ static int conv_device(int P, const double *d_a, int n, const double *d_b, int m
      * bins 0..P/2 only (real.c:169-179): compact spectra of P/2+1 bins give the same bits
      * with a third less traffic */
     const long long cd = P / 2 + 1;
-    double *pa = hs_scratch(7, sizeof(double) * (size_t)P * 2 * (size_t)batch);
-    fft_data *spec = hs_scratch(10, sizeof(fft_data) * (size_t)cd * 2 * (size_t)batch);
+    double *pa = hs_scratch(HS_SCR_CONV_PAD, sizeof(double) * (size_t)P * 2 * (size_t)batch);
+    fft_data *spec = hs_scratch(HS_SCR_CONV_SPEC, sizeof(fft_data) * (size_t)cd * 2 * (size_t)batch);
     if (!pa || !spec) {
         conv_plans_done(cp);
         hs_seterr("convolution scratch allocation failed (%d rows of P = %d)", batch, P);
@@ -207,7 +207,7 @@ static int conv_device(int P, const double *d_a, int n, const double *d_b, int m
                  ? HSFFT_ERR_DEVICE : 0;
     if (!rc) rc = hsfft_r2c_batched_compact(f, pa, A, batch);
     if (!rc) rc = hsfft_r2c_batched_compact(f, pb, B, batch);
-    if (!rc) rc = hs_c2r_product_rows(iv, A, B, cd, d_res, batch); /* product fused into the pre-twiddle */
+    if (!rc) rc = hs_c2r_rows(iv, A, B, cd, d_res, batch); /* product fused into the pre-twiddle */
     if (!rc && scale) rc = hsd_scale_real(d_res, P, batch, P, (double)P) ? HSFFT_ERR_DEVICE : 0;
     if (!rc) rc = hsd_sync() ? HSFFT_ERR_DEVICE : 0;
     conv_plans_done(cp);
@@ -228,7 +228,7 @@ static int convolve_locked(const char *type, const char *conv_type, fft_type *in
         exit(EXIT_FAILURE);
     }
     const int len = conv_window(type, linear, clen, P, length1, length2, &start);
-    double *d_a = hs_scratch(5, sizeof(double) * (size_t)(length1 + length2));
+    double *d_a = hs_scratch(HS_SCR_CONV_IN, sizeof(double) * (size_t)(length1 + length2));
     double *d_res = hsfft_malloc(sizeof(double) * (size_t)P);
     if (!d_a || !d_res) {
         hsfft_free(d_res);

@@ -4,6 +4,8 @@
 #ifndef HSFFT_HOST_H_
 #define HSFFT_HOST_H_
 
+#include <stdlib.h>
+
 #include "highspeedFFT.h"
 #include "hsfft_internal.h"
 #include "real.h"
@@ -58,7 +60,22 @@ void hs_longvector(fft_data *tw, int M, const int *fac, int lf, int exact);
 int hs_bluestein_M_init(int N); /* fft_init sizing (log10), ref :242-252 */
 int hs_bluestein_M_exec(int N); /* bluestein_fft sizing (log2), ref :1750-1751 */
 
-/* registry / scheduling / execution (hsfft_exec.c).  hs_entry_get returns the entry with a
+/* a length the reference runs as one leaf butterfly (ref :332-713); every other radix uses
+ * the odd-radix constants */
+static inline int hs_is_leaf_radix(int r) { return r == 2 || r == 3 || r == 4 || r == 5 || r == 7 || r == 8; }
+/* integer knob (hs_getenv: served from the small path's snapshot inside fft_exec) */
+static inline int hs_env_int(const char *name, int dflt)
+{
+    const char *s = hs_getenv(name);
+    return s ? atoi(s) : dflt;
+}
+/* pass schedule of e->M (hsfft_schedule.c): stages, passes with tiles and variants, odd-radix
+ * constants; nonzero (hs_seterr set where there is something to say) if M cannot be scheduled */
+int hs_build_schedule(hs_entry *e);
+/* HSFFT_CRASH_TRACE=1 (hsfft_crash.c): install the crash-trace signal handlers */
+void hs_crash_trace_install(void);
+
+/* registry / execution (hsfft_exec.c).  hs_entry_get returns the entry with a
  * reference held; every successful get is paired with hs_entry_put. */
 hs_entry *hs_entry_get(const struct fft_set *obj);
 void hs_entry_put(hs_entry *e);
@@ -76,13 +93,39 @@ int hs_c2c_rows(hs_entry *e, const void *in, long long idist, void *out, long lo
  * not allow it (caller falls back to c2c + split), 0 on success, < 0 on error */
 int hs_r2c_fused(hs_entry *e, const void *in, long long idist, void *Z, void *X, long long xdist, const void *tw2,
                  int batch, int compact);
-/* scratch buffers per device: class 0..2 chain pool, 3 Bluestein mid, 4 real staging, 5-7 misc,
- * 8 Bluestein second mid, 9 host pipeline, 10 convolution spectra */
-int hs_c2r_rows(fft_real_object r, const fft_data *d_in, long long xdist, fft_type *d_out, int batch);
-/* c2r of the product d_a .* d_b (compact or reference-layout rows xdist apart) */
-int hs_c2r_product_rows(fft_real_object r, const fft_data *d_a, const fft_data *d_b, long long xdist, fft_type *d_out,
-                        int batch);
+/* c2r of rows xdist complex apart (hsfft_real.c); d_b != NULL: of the product d_a .* d_b */
+int hs_c2r_rows(fft_real_object r, const fft_data *d_a, const fft_data *d_b, long long xdist, fft_type *d_out,
+                int batch);
+/* Scratch buffers, one per class and device, grown on demand and used under the device lock.
+ * Two names with one number share a buffer: their users are separate public entry points that
+ * hold the device lock for their whole call, wait for the device before they return, and never
+ * call each other, so the buffer is never live for both. */
+enum {
+    HS_SCR_CHAIN0 = 0,    /* intermediates of a pass chain, alternating */
+    HS_SCR_CHAIN1 = 1,
+    HS_SCR_SPARE = 2,     /* unused (kept: the pool's size is unchanged) */
+    HS_SCR_BLUE_MID = 3,  /* Bluestein M-point intermediate, or the persistent launch's images */
+    HS_SCR_REAL_Z = 4,    /* real transforms: the inner c2c's N/2-point rows */
+    HS_SCR_STAGE_IN = 5,  /* drop-in fft_exec / fft_r2c_exec / fft_c2r_exec: staged input */
+    HS_SCR_CONV_IN = 5,   /* drop-in fft_convolve: both uploaded signals (it runs the batched
+                           * real transforms, never the drop-in ones) */
+    HS_SCR_STAGE_OUT = 6, /* drop-in staged output */
+    HS_SCR_HOST_IN = 7,   /* hsfft_exec_batched_host: two upload slots (it runs c2c rows only) */
+    HS_SCR_CONV_PAD = 7,  /* convolution: both zero-padded signals (it runs real transforms only) */
+    HS_SCR_BLUE_MID2 = 8, /* Bluestein second intermediate (fused middle kernel) */
+    HS_SCR_HOST_OUT = 9,  /* hsfft_exec_batched_host: two download slots */
+    HS_SCR_CONV_SPEC = 10,/* convolution: both compact spectra */
+    HS_NSCRATCH = 11
+};
 void *hs_scratch(int cls, size_t bytes);
+/* Staging of the drop-in entry points (device lock held).  Caller buffers are used directly
+ * only when BOTH are device pointers; otherwise both sides go through the staging slots.
+ * hs_stage_in sizes both slots (*di, *dq) and copies copy_bytes of the caller's input into *di
+ * -- d2d for a device pointer, h2d for a host one; returns 1 if a slot could not be allocated,
+ * else the copy's result.  hs_stage_out copies the output slot to the caller's buffer. */
+int hs_stage_in(const void *p, int on_device, size_t copy_bytes, size_t in_bytes, size_t out_bytes, void **di,
+                void **dq);
+int hs_stage_out(void *p, int on_device, const void *dq, size_t bytes);
 /* brackets a synchronous entry point on this thread (1 enter, 0 leave): persistent Bluestein
  * launches inside it wait and re-run timed-out rows instead of reporting them later */
 void hs_sync_call(int enter);

@@ -10,7 +10,7 @@
  *   fft_init     ref :206-286
  *   free_fft     ref :2315-2318
  * The plan bytes (struct fft_set + twiddles) equal the reference's for the same N and sgn
- * in the default "reference" twiddle mode (tests/test_product_planner.py).  Trig values
+ * in the default "reference" twiddle mode (tests/test_product_cpu.py).  Trig values
  * come from glibc sincos, which is what GCC -O2 fuses the reference's cos/sin pairs into.
  */
 #define _GNU_SOURCE

@@ -112,7 +112,7 @@ void hs_real_release_device(int dev)
     pthread_mutex_unlock(&g_rlock);
 }
 
-/* row chunk for the inner c2c's intermediate Z (scratch class 4): HSFFT_CHUNK_MB of Z per
+/* row chunk for the inner c2c's intermediate Z (HS_SCR_REAL_Z): HSFFT_REAL_CHUNK_MB of Z per
  * chunk, default 16 GiB (measured, 4096 x 2^22 r2c, fused split: 2 GiB 91.7, 4 GiB 94.1,
  * 8 GiB 98.3, 16 GiB 99.9 GSamples/s -- longer launches fill the chip better); halved while
  * the allocation fails, so a device with less free HBM still runs, in smaller chunks */
@@ -123,7 +123,7 @@ static fft_data *real_chunk(int h, int batch, long long *chunk)
     if (rows < 1) rows = 1;
     if (rows > batch) rows = batch;
     for (;;) {
-        fft_data *Z = hs_scratch(4, sizeof(fft_data) * (size_t)(rows * h));
+        fft_data *Z = hs_scratch(HS_SCR_REAL_Z, sizeof(fft_data) * (size_t)(rows * h));
         if (Z || rows == 1) {
             *chunk = rows;
             if (!Z) hs_seterr("scratch allocation of %lld bytes failed", (long long)(rows * h * 16));
@@ -133,145 +133,96 @@ static fft_data *real_chunk(int h, int batch, long long *chunk)
     }
 }
 
-static int r2c_locked(fft_real_object r, hs_entry *e, const fft_type *d_in, fft_data *d_out, int batch);
-
-int hsfft_r2c_batched(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch)
+/* (device lock held) r2c of `batch` rows.  compact 0: the reference's mirrored rows of N bins;
+ * 1: bins 0..N/2 per row (rows of N/2+1 complex), the non-redundant half
+ * -- 16 B written per real sample instead of 24 for the same values (bit-identical to bins
+ * 0..N/2 of the mirrored rows) */
+static int r2c_rows(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch, int compact)
 {
-    if (!r || !r->cobj || !d_in || !d_out || batch < 0) {
-        hs_seterr("hsfft_r2c_batched: invalid arguments");
-        return HSFFT_ERR_ARG;
-    }
-    if (batch == 0) return 0;
-    int rc = hs_require_gpu();
-    if (rc) return rc;
-    const int d = hs_lock_device();
     hs_entry *e = hs_entry_get(r->cobj);
-    rc = e ? r2c_locked(r, e, d_in, d_out, batch) : HSFFT_ERR_DEVICE;
+    void *tw2 = e ? tw2_device(r) : NULL;
+    const int h = r->cobj->N, N = 2 * h;
+    const long long xdist = compact ? h + 1 : N;
+    long long chunk = 1;
+    fft_data *Z = tw2 ? real_chunk(h, batch, &chunk) : NULL;
+    int rc = !tw2 ? HSFFT_ERR_DEVICE : !Z ? HSFFT_ERR_NOMEM : 0;
+    for (long long c0 = 0; c0 < batch && !rc; c0 += chunk) {
+        const int cb = (int)(batch - c0 < chunk ? batch - c0 : chunk);
+        fft_data *X = d_out + c0 * xdist;
+        /* x[2k], x[2k+1] packed as complex = the same bytes (ref real.c:99-103) */
+        rc = hs_r2c_fused(e, d_in + c0 * N, h, Z, X, xdist, tw2, cb, compact);
+        if (rc == 1) {
+            rc = hs_c2c_rows(e, d_in + c0 * N, h, Z, h, cb);
+            if (!rc) rc = (compact ? hsd_r2c_post_compact : hsd_r2c_post)(Z, tw2, X, h, cb, h, xdist) ? HSFFT_ERR_DEVICE : 0;
+        }
+    }
     hs_entry_put(e);
-    hs_unlock_device(d);
     return rc;
 }
 
-static int r2c_locked(fft_real_object r, hs_entry *e, const fft_type *d_in, fft_data *d_out, int batch)
+/* (callers hold the device lock) c2r of rows xdist complex apart (the reference layout: N;
+ * compact spectra: N/2+1 -- the pre-twiddle reads bins 0..N/2 only, ref real.c:169-179); with
+ * d_b, of the product d_a .* d_b, multiplied inside the pre-twiddle */
+int hs_c2r_rows(fft_real_object r, const fft_data *d_a, const fft_data *d_b, long long xdist, fft_type *d_out,
+                int batch)
 {
-    int rc = 0;
-    void *tw2 = tw2_device(r);
-    if (!tw2) return HSFFT_ERR_DEVICE;
+    hs_entry *e = hs_entry_get(r->cobj);
+    void *tw2 = e ? tw2_device(r) : NULL;
     const int h = r->cobj->N, N = 2 * h;
-    long long chunk;
-    fft_data *Z = real_chunk(h, batch, &chunk);
-    if (!Z) return HSFFT_ERR_NOMEM;
-    for (long long c0 = 0; c0 < batch; c0 += chunk) {
+    long long chunk = 1;
+    fft_data *Zi = tw2 ? real_chunk(h, batch, &chunk) : NULL;
+    int rc = !tw2 ? HSFFT_ERR_DEVICE : !Zi ? HSFFT_ERR_NOMEM : 0;
+    for (long long c0 = 0; c0 < batch && !rc; c0 += chunk) {
         const int cb = (int)(batch - c0 < chunk ? batch - c0 : chunk);
-        /* x[2k], x[2k+1] packed as complex = the same bytes (ref real.c:99-103) */
-        rc = hs_r2c_fused(e, d_in + c0 * N, h, Z, d_out + c0 * N, N, tw2, cb, 0);
-        if (rc == 1) {
-            rc = hs_c2c_rows(e, d_in + c0 * N, h, Z, h, cb);
-            if (!rc) rc = hsd_r2c_post(Z, tw2, d_out + c0 * N, h, cb, h, N) ? HSFFT_ERR_DEVICE : 0;
-        }
-        if (rc) return rc;
+        rc = d_b ? hsd_c2r_pre_mul(d_a + c0 * xdist, d_b + c0 * xdist, tw2, Zi, h, cb, xdist, h)
+                 : hsd_c2r_pre(d_a + c0 * xdist, tw2, Zi, h, cb, xdist, h);
+        if (rc) rc = HSFFT_ERR_DEVICE;
+        /* unpacking complex_output into interleaved reals is again a reinterpretation */
+        if (!rc) rc = hs_c2c_rows(e, Zi, h, d_out + c0 * N, h, cb);
     }
+    hs_entry_put(e);
+    return rc;
+}
+
+/* argument and GPU check of the batched entry points, then the device lock: 0 with the device
+ * locked (*dev), 1 for an empty batch (nothing to do, not locked), < 0 on error */
+static int real_enter(const char *who, fft_real_object r, const void *d_in, const void *d_out, int batch, int *dev)
+{
+    if (!r || !r->cobj || !d_in || !d_out || batch < 0) {
+        hs_seterr("%s: invalid arguments", who);
+        return HSFFT_ERR_ARG;
+    }
+    if (batch == 0) return 1;
+    const int rc = hs_require_gpu();
+    if (rc) return rc;
+    *dev = hs_lock_device();
     return 0;
 }
 
-/* compact r2c: bins 0..N/2 per row (rows of N/2+1 complex), the
- * non-redundant half of the reference's mirrored output -- 16 B written per real sample
- * instead of 24 for the same values (bit-identical to bins 0..N/2 of hsfft_r2c_batched) */
-static int r2c_compact_locked(fft_real_object r, hs_entry *e, const fft_type *d_in, fft_data *d_out, int batch);
-
-int hsfft_r2c_batched_compact(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch)
+int hsfft_r2c_batched(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch)
 {
-    if (!r || !r->cobj || !d_in || !d_out || batch < 0) {
-        hs_seterr("hsfft_r2c_batched_compact: invalid arguments");
-        return HSFFT_ERR_ARG;
-    }
-    if (batch == 0) return 0;
-    int rc = hs_require_gpu();
-    if (rc) return rc;
-    const int d = hs_lock_device();
-    hs_entry *e = hs_entry_get(r->cobj);
-    rc = e ? r2c_compact_locked(r, e, d_in, d_out, batch) : HSFFT_ERR_DEVICE;
-    hs_entry_put(e);
+    int d, rc = real_enter("hsfft_r2c_batched", r, d_in, d_out, batch, &d);
+    if (rc) return rc < 0 ? rc : 0;
+    rc = r2c_rows(r, d_in, d_out, batch, 0);
     hs_unlock_device(d);
     return rc;
 }
 
-static int r2c_compact_locked(fft_real_object r, hs_entry *e, const fft_type *d_in, fft_data *d_out, int batch)
+int hsfft_r2c_batched_compact(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch)
 {
-    int rc = 0;
-    void *tw2 = tw2_device(r);
-    if (!tw2) return HSFFT_ERR_DEVICE;
-    const int h = r->cobj->N, N = 2 * h;
-    long long chunk;
-    fft_data *Z = real_chunk(h, batch, &chunk);
-    if (!Z) return HSFFT_ERR_NOMEM;
-    for (long long c0 = 0; c0 < batch && !rc; c0 += chunk) {
-        const int cb = (int)(batch - c0 < chunk ? batch - c0 : chunk);
-        rc = hs_r2c_fused(e, d_in + c0 * N, h, Z, d_out + c0 * (h + 1), h + 1, tw2, cb, 1);
-        if (rc == 1) {
-            rc = hs_c2c_rows(e, d_in + c0 * N, h, Z, h, cb);
-            if (!rc)
-                rc = hsd_r2c_post_compact(Z, tw2, d_out + c0 * (h + 1), h, cb, h, h + 1) ? HSFFT_ERR_DEVICE : 0;
-        }
-    }
+    int d, rc = real_enter("hsfft_r2c_batched_compact", r, d_in, d_out, batch, &d);
+    if (rc) return rc < 0 ? rc : 0;
+    rc = r2c_rows(r, d_in, d_out, batch, 1);
+    hs_unlock_device(d);
     return rc;
 }
 
 int hsfft_c2r_batched(fft_real_object r, const fft_data *d_in, fft_type *d_out, int batch)
 {
-    if (!r || !r->cobj || !d_in || !d_out || batch < 0) {
-        hs_seterr("hsfft_c2r_batched: invalid arguments");
-        return HSFFT_ERR_ARG;
-    }
-    if (batch == 0) return 0;
-    int rc = hs_require_gpu();
-    if (rc) return rc;
-    const int d = hs_lock_device();
-    rc = hs_c2r_rows(r, d_in, 2LL * r->cobj->N, d_out, batch);
+    int d, rc = real_enter("hsfft_c2r_batched", r, d_in, d_out, batch, &d);
+    if (rc) return rc < 0 ? rc : 0;
+    rc = hs_c2r_rows(r, d_in, NULL, 2LL * r->cobj->N, d_out, batch);
     hs_unlock_device(d);
-    return rc;
-}
-
-/* (callers hold the device lock) */
-int hs_c2r_product_rows(fft_real_object r, const fft_data *d_a, const fft_data *d_b, long long xdist, fft_type *d_out,
-                        int batch)
-{
-    int rc = 0;
-    hs_entry *e = hs_entry_get(r->cobj);
-    void *tw2 = e ? tw2_device(r) : NULL;
-    const int h = r->cobj->N, N = 2 * h;
-    long long chunk = 1;
-    fft_data *Zi = tw2 ? real_chunk(h, batch, &chunk) : NULL;
-    if (!tw2) rc = HSFFT_ERR_DEVICE;
-    else if (!Zi) rc = HSFFT_ERR_NOMEM;
-    for (long long c0 = 0; c0 < batch && !rc; c0 += chunk) {
-        const int cb = (int)(batch - c0 < chunk ? batch - c0 : chunk);
-        rc = hsd_c2r_pre_mul(d_a + c0 * xdist, d_b + c0 * xdist, tw2, Zi, h, cb, xdist, h) ? HSFFT_ERR_DEVICE : 0;
-        if (!rc) rc = hs_c2c_rows(e, Zi, h, d_out + c0 * N, h, cb);
-    }
-    hs_entry_put(e);
-    return rc;
-}
-
-/* c2r of rows xdist complex apart (the reference layout: N; compact spectra: N/2+1 -- the
- * pre-twiddle reads bins 0..N/2 only, ref real.c:169-179) */
-int hs_c2r_rows(fft_real_object r, const fft_data *d_in, long long xdist, fft_type *d_out, int batch)
-{
-    int rc = 0;
-    hs_entry *e = hs_entry_get(r->cobj);
-    void *tw2 = e ? tw2_device(r) : NULL;
-    const int h = r->cobj->N, N = 2 * h;
-    long long chunk = 1;
-    fft_data *Zi = tw2 ? real_chunk(h, batch, &chunk) : NULL;
-    if (!tw2) rc = HSFFT_ERR_DEVICE;
-    else if (!Zi) rc = HSFFT_ERR_NOMEM;
-    for (long long c0 = 0; c0 < batch && !rc; c0 += chunk) {
-        const int cb = (int)(batch - c0 < chunk ? batch - c0 : chunk);
-        rc = hsd_c2r_pre(d_in + c0 * xdist, tw2, Zi, h, cb, xdist, h) ? HSFFT_ERR_DEVICE : 0;
-        /* unpacking complex_output into interleaved reals is again a reinterpretation */
-        if (!rc) rc = hs_c2c_rows(e, Zi, h, d_out + c0 * N, h, cb);
-    }
-    hs_entry_put(e);
     return rc;
 }
 
@@ -289,76 +240,47 @@ int hsfft_time_r2c_batched(fft_real_object r, const fft_type *d_in, fft_data *d_
     return rc;
 }
 
-static void real_fail(const char *what)
+static void real_fail(const char *who, const char *what)
 {
-    fprintf(stderr, "Error: %s (%s)\n", what, hsfft_last_error());
+    fprintf(stderr, "Error: %s%s (%s)\n", who, what, hsfft_last_error());
     exit(EXIT_FAILURE);
 }
 
-static void r2c_exec_locked(fft_real_object r, fft_type *inp, fft_data *oup)
+/* The drop-in pair: one row through the batched entry point, on the caller's buffers when both
+ * are device pointers, else staged (hs_stage_in); synchronous.  c2r reads bins 0..N/2 only
+ * (real.c:169-179), so h+1 bins are uploaded into a staging row N bins long. */
+static void real_exec_locked(fft_real_object r, int inverse, void *inp, void *oup)
 {
+    const char *who = inverse ? "fft_c2r_exec" : "fft_r2c_exec";
     if (r == NULL || inp == NULL || oup == NULL) {
         fprintf(stderr, "Error: Invalid real FFT object or data pointers\n");
         exit(EXIT_FAILURE);
     }
-    if (hs_require_gpu()) real_fail("fft_r2c_exec needs an MI355X");
-    const int N = 2 * r->cobj->N;
-    const int din = hsd_is_device_ptr(inp), dout = hsd_is_device_ptr(oup);
-    int rc;
-    if (din && dout) {
-        rc = hsfft_r2c_batched(r, inp, oup, 1);
-    } else {
-        double *di = hs_scratch(5, sizeof(double) * (size_t)N);
-        fft_data *dq = hs_scratch(6, sizeof(fft_data) * (size_t)N);
-        if (!di || !dq) real_fail("fft_r2c_exec: staging allocation failed");
-        rc = din ? hsd_d2d_async(di, inp, sizeof(double) * (size_t)N) : hsd_h2d(di, inp, sizeof(double) * (size_t)N);
-        if (!rc) rc = hsfft_r2c_batched(r, di, dq, 1);
-        if (!rc) rc = dout ? hsd_d2d_async(oup, dq, sizeof(fft_data) * (size_t)N) : hsd_d2h(oup, dq, sizeof(fft_data) * (size_t)N);
-    }
-    if (!rc) rc = hsd_sync();
-    if (rc) real_fail("fft_r2c_exec failed");
-}
-
-void fft_r2c_exec(fft_real_object r, fft_type *inp, fft_data *oup)
-{
-    const int d = hs_lock_device();
-    hs_sync_call(1); /* synchronous: a Bluestein inner plan re-runs timed-out rows itself */
-    r2c_exec_locked(r, inp, oup);
-    hs_sync_call(0);
-    hs_unlock_device(d);
-}
-
-static void c2r_exec_locked(fft_real_object r, fft_data *inp, fft_type *oup)
-{
-    if (r == NULL || inp == NULL || oup == NULL) {
-        fprintf(stderr, "Error: Invalid real FFT object or data pointers\n");
-        exit(EXIT_FAILURE);
-    }
-    if (hs_require_gpu()) real_fail("fft_c2r_exec needs an MI355X");
+    if (hs_require_gpu()) real_fail(who, " needs an MI355X");
     const int h = r->cobj->N, N = 2 * h;
+    const size_t rbytes = sizeof(double) * (size_t)N, cbytes = sizeof(fft_data) * (size_t)N;
+    const size_t in_bytes = inverse ? cbytes : rbytes, out_bytes = inverse ? rbytes : cbytes;
     const int din = hsd_is_device_ptr(inp), dout = hsd_is_device_ptr(oup);
-    int rc;
-    if (din && dout) {
-        rc = hsfft_c2r_batched(r, inp, oup, 1);
-    } else {
-        /* only bins 0..N/2 are read (real.c:169-179); the staging row is N long */
-        fft_data *di = hs_scratch(5, sizeof(fft_data) * (size_t)N);
-        double *dq = hs_scratch(6, sizeof(double) * (size_t)N);
-        if (!di || !dq) real_fail("fft_c2r_exec: staging allocation failed");
-        rc = din ? hsd_d2d_async(di, inp, sizeof(fft_data) * (size_t)(h + 1))
-                 : hsd_h2d(di, inp, sizeof(fft_data) * (size_t)(h + 1));
-        if (!rc) rc = hsfft_c2r_batched(r, di, dq, 1);
-        if (!rc) rc = dout ? hsd_d2d_async(oup, dq, sizeof(double) * (size_t)N) : hsd_d2h(oup, dq, sizeof(double) * (size_t)N);
+    void *di = inp, *dq = oup;
+    int rc = 0;
+    if (!(din && dout)) {
+        rc = hs_stage_in(inp, din, inverse ? sizeof(fft_data) * (size_t)(h + 1) : rbytes, in_bytes, out_bytes, &di, &dq);
+        if (rc == 1) real_fail(who, ": staging allocation failed");
     }
+    if (!rc) rc = inverse ? hsfft_c2r_batched(r, di, dq, 1) : hsfft_r2c_batched(r, di, dq, 1);
+    if (!rc && dq != oup) rc = hs_stage_out(oup, dout, dq, out_bytes);
     if (!rc) rc = hsd_sync();
-    if (rc) real_fail("fft_c2r_exec failed");
+    if (rc) real_fail(who, " failed");
 }
 
-void fft_c2r_exec(fft_real_object r, fft_data *inp, fft_type *oup)
+static void real_exec(fft_real_object r, int inverse, void *inp, void *oup)
 {
     const int d = hs_lock_device();
     hs_sync_call(1); /* synchronous: a Bluestein inner plan re-runs timed-out rows itself */
-    c2r_exec_locked(r, inp, oup);
+    real_exec_locked(r, inverse, inp, oup);
     hs_sync_call(0);
     hs_unlock_device(d);
 }
+
+void fft_r2c_exec(fft_real_object r, fft_type *inp, fft_data *oup) { real_exec(r, 0, inp, oup); }
+void fft_c2r_exec(fft_real_object r, fft_data *inp, fft_type *oup) { real_exec(r, 1, inp, oup); }

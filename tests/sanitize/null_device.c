@@ -7,7 +7,14 @@
  * touches the first and last element of every row it would read or write, so an undersized
  * scratch buffer or a wrong row stride is an AddressSanitizer report.  It is never linked
  * into the product.
+ *
+ * HSFFT_NULL_TRACE=<file>: every launching entry (passes, the Bluestein / real / convolution
+ * kernels, the copies, stream selection) appends one line to <file>: its name, its scalar
+ * arguments and, for its buffers, only whether in == out (`io`) and whether in is the previous
+ * line's out (`chain`) -- never an address, so the trace of a deterministic caller is the same
+ * bytes on every run (tests/golden/launch_trace.txt, written by trace_driver.c).
  */
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <pthread.h>
@@ -20,6 +27,39 @@
 static __thread char err[256];
 static __thread int sidx;
 static __thread volatile double sink; /* per thread: launches on different null devices run concurrently */
+
+static FILE *trace_fp;
+static pthread_once_t trace_once = PTHREAD_ONCE_INIT;
+static pthread_mutex_t trace_mtx = PTHREAD_MUTEX_INITIALIZER;
+static const void *trace_prev_out;
+
+static void trace_open(void)
+{
+    const char *path = getenv("HSFFT_NULL_TRACE");
+    if (path && path[0]) trace_fp = fopen(path, "a");
+}
+
+/* one trace line: "<fmt...> io=<in == out> chain=<in == previous out>"; has_io 0: no buffers */
+__attribute__((format(printf, 4, 5))) static void trace(int has_io, const void *in, const void *out, const char *fmt, ...)
+{
+    pthread_once(&trace_once, trace_open);
+    if (!trace_fp) return;
+    pthread_mutex_lock(&trace_mtx);
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(trace_fp, fmt, ap);
+    va_end(ap);
+    if (has_io) {
+        fprintf(trace_fp, " io=%d chain=%d", in == out, in == trace_prev_out);
+        trace_prev_out = out;
+    }
+    fputc('\n', trace_fp);
+    fflush(trace_fp);
+    pthread_mutex_unlock(&trace_mtx);
+}
+
+/* a line of the caller's own (trace_driver.c marks its scenarios) */
+void null_trace_note(const char *text) { trace(0, NULL, NULL, "# %s", text); }
 
 /* HSFFT_NULL_NDEV (default 1) null devices, so that the multi-device paths
  * (hsfft_exec_multi: one host thread per device, per-device state, locks and scratch) run
@@ -47,16 +87,19 @@ int hsd_free(void *p)
 }
 int hsd_h2d(void *d, const void *h, size_t bytes)
 {
+    trace(1, h, d, "h2d bytes=%zu", bytes);
     memcpy(d, h, bytes);
     return 0;
 }
 int hsd_d2h(void *h, const void *d, size_t bytes)
 {
+    trace(1, d, h, "d2h bytes=%zu", bytes);
     memcpy(h, d, bytes);
     return 0;
 }
 int hsd_d2d_async(void *d, const void *s, size_t bytes)
 {
+    trace(1, s, d, "d2d bytes=%zu", bytes);
     memmove(d, s, bytes);
     return 0;
 }
@@ -87,12 +130,23 @@ int hsd_finalize_device(void)
 }
 int hsd_select_stream(int idx)
 {
+    trace(0, NULL, NULL, "select_stream %d", idx);
     sidx = idx;
     return 0;
 }
 int hsd_stream_index(void) { return sidx; }
-int hsd_h2d_async(void *d, const void *h, size_t bytes) { return hsd_h2d(d, h, bytes); }
-int hsd_d2h_async(void *h, const void *d, size_t bytes) { return hsd_d2h(h, d, bytes); }
+int hsd_h2d_async(void *d, const void *h, size_t bytes)
+{
+    trace(1, h, d, "h2d_async bytes=%zu", bytes);
+    memcpy(d, h, bytes);
+    return 0;
+}
+int hsd_d2h_async(void *h, const void *d, size_t bytes)
+{
+    trace(1, d, h, "d2h_async bytes=%zu", bytes);
+    memcpy(h, d, bytes);
+    return 0;
+}
 int hsd_stream_sync(void) { return 0; }
 int hsd_host_word_wait(unsigned *flag, unsigned v)
 {
@@ -254,6 +308,11 @@ static void touch_rows_w(void *base, long long dist, long long len, long long ro
 
 int hsd_run_pass(const hsd_pass *p, const hsd_launch *l)
 {
+    trace(1, l->in, l->out,
+          "run_pass P=%d A=%lld B=%lld G=%d Wq=%d v=%d idist=%lld odist=%lld batch=%d sgn=%d conj=%d dir=%d load=%d "
+          "store=%d nsig=%lld tw_t=%d done=%d",
+          p->P, p->A, p->B, p->G, p->Wq, p->variant, l->idist, l->odist, l->batch, l->sgn, l->conj, l->dir, l->load_op,
+          l->store_op, l->nsig, l->tw_t, l->done != NULL);
     if (p->P <= 0 || p->A <= 0 || p->B <= 0 || l->batch <= 0) {
         snprintf(err, sizeof err, "null device: bad pass geometry");
         return -1;
@@ -295,6 +354,8 @@ int mr_has_variant(const hsd_pass *p) { return 1; }
 int hsd_r2c_last(const void *Z, long long zdist, void *X, long long xdist, const void *tw, const void *w2, long long h,
                  long long B, int batch, int sgn, int compact)
 {
+    trace(1, Z, X, "r2c_last zdist=%lld xdist=%lld h=%lld B=%lld batch=%d sgn=%d compact=%d", zdist, xdist, h, B, batch,
+          sgn, compact);
     touch_rows_r(Z, zdist, h, batch, 16);
     touch_rows_r(w2, 0, h, 1, 16);
     touch_rows_w(X, xdist, compact ? h + 1 : 2 * h, batch, 16);
@@ -303,6 +364,8 @@ int hsd_r2c_last(const void *Z, long long zdist, void *X, long long xdist, const
 int hsd_blue_mid(const void *in, void *out, long long dist, const void *tw, const void *hk, int batch, int sgn,
                  int conj, int dir, int sgn2, int conj2)
 {
+    trace(1, in, out, "blue_mid dist=%lld batch=%d sgn=%d conj=%d dir=%d sgn2=%d conj2=%d", dist, batch, sgn, conj, dir,
+          sgn2, conj2);
     touch_rows_r(in, dist, dist, batch, 16);
     touch_rows_r(hk, 0, dist, 1, 16);
     touch_rows_w(out, dist, dist, batch, 16);
@@ -311,6 +374,7 @@ int hsd_blue_mid(const void *in, void *out, long long dist, const void *tw, cons
 int hsd_blue_last(const void *in, long long idist, void *out, long long odist, const void *tw, const void *chirp,
                   long long nsig, int batch, int dir)
 {
+    trace(1, in, out, "blue_last idist=%lld odist=%lld nsig=%lld batch=%d dir=%d", idist, odist, nsig, batch, dir);
     touch_rows_r(in, idist, idist, batch, 16);
     touch_rows_w(out, odist, nsig, batch, 16);
     return 0;
@@ -318,6 +382,7 @@ int hsd_blue_last(const void *in, long long idist, void *out, long long odist, c
 int hsd_blue_first(const void *in, long long idist, void *out, long long odist, const void *tw, const void *chirp,
                    long long nsig, int batch, int dir)
 {
+    trace(1, in, out, "blue_first idist=%lld odist=%lld nsig=%lld batch=%d dir=%d", idist, odist, nsig, batch, dir);
     touch_rows_r(in, idist, nsig, batch, 16);
     touch_rows_r(chirp, 0, nsig, 1, 16);
     touch_rows_w(out, odist, odist, batch, 16);
@@ -339,6 +404,8 @@ int hsd_blue_deferred_take(void)
 int hsd_blue_xcd(const void *in, long long idist, void *out, long long odist, const void *tw, const void *chirp,
                  const void *hk, void *img, size_t img_bytes, long long nsig, int batch, int sgn, int ng, int sync)
 {
+    trace(1, in, out, "blue_xcd idist=%lld odist=%lld img_bytes=%zu nsig=%lld batch=%d sgn=%d ng=%d sync=%d", idist, odist,
+          img_bytes, nsig, batch, sgn, ng, sync);
     touch_rows_r(in, idist, nsig, batch, 16);
     touch_rows_r(chirp, 0, nsig, 1, 16);
     touch_rows_r(hk, 0, 512 * 512, 1, 16);
@@ -365,24 +432,28 @@ int hsd_fill_real(void *d, int64_t count, uint64_t seed, uint64_t offset)
 }
 int hsd_r2c_post(const void *Z, const void *tw2, void *X, int h, int batch, long long zdist, long long xdist)
 {
+    trace(1, Z, X, "r2c_post h=%d batch=%d zdist=%lld xdist=%lld", h, batch, zdist, xdist);
     touch_rows_r(Z, zdist, h, batch, 16);
     touch_rows_w(X, xdist, 2LL * h, batch, 16);
     return 0;
 }
 int hsd_r2c_post_compact(const void *Z, const void *tw2, void *X, int h, int batch, long long zdist, long long xdist)
 {
+    trace(1, Z, X, "r2c_post_compact h=%d batch=%d zdist=%lld xdist=%lld", h, batch, zdist, xdist);
     touch_rows_r(Z, zdist, h, batch, 16);
     touch_rows_w(X, xdist, h + 1LL, batch, 16);
     return 0;
 }
 int hsd_c2r_pre(const void *X, const void *tw2, void *Zin, int h, int batch, long long xdist, long long zdist)
 {
+    trace(1, X, Zin, "c2r_pre h=%d batch=%d xdist=%lld zdist=%lld", h, batch, xdist, zdist);
     touch_rows_r(X, xdist, h + 1LL, batch, 16);
     touch_rows_w(Zin, zdist, h, batch, 16);
     return 0;
 }
 int hsd_cmul(const void *A, const void *Bv, void *C, long long n, int batch, long long dist)
 {
+    trace(1, A, C, "cmul n=%lld batch=%d dist=%lld", n, batch, dist);
     touch_rows_r(A, dist, n, batch, 16);
     touch_rows_r(Bv, dist, n, batch, 16);
     touch_rows_w(C, dist, n, batch, 16);
@@ -391,6 +462,7 @@ int hsd_cmul(const void *A, const void *Bv, void *C, long long n, int batch, lon
 int hsd_c2r_pre_mul(const void *A, const void *Bv, const void *tw2, void *Zin, int h, int batch, long long xdist,
                     long long zdist)
 {
+    trace(1, A, Zin, "c2r_pre_mul h=%d batch=%d xdist=%lld zdist=%lld", h, batch, xdist, zdist);
     touch_rows_r(A, xdist, h + 1LL, batch, 16);
     touch_rows_r(Bv, xdist, h + 1LL, batch, 16);
     touch_rows_w(Zin, zdist, h, batch, 16);
@@ -399,18 +471,23 @@ int hsd_c2r_pre_mul(const void *A, const void *Bv, const void *tw2, void *Zin, i
 int hsd_copy_rows_div(const void *src, long long sdist, long long soff, void *dst, long long ddist, long long n,
                       int batch, double divisor)
 {
+    trace(1, src, dst, "copy_rows_div sdist=%lld soff=%lld ddist=%lld n=%lld batch=%d divisor=%g", sdist, soff, ddist, n,
+          batch, divisor);
     touch_rows_r((const double *)src + soff, sdist, n, batch, 8);
     touch_rows_w(dst, ddist, n, batch, 8);
     return 0;
 }
 int hsd_scale_real(void *x, long long n, int batch, long long dist, double divisor)
 {
+    trace(1, x, x, "scale_real n=%lld batch=%d dist=%lld divisor=%g", n, batch, dist, divisor);
     touch_rows_w(x, dist, n, batch, 8);
     return 0;
 }
 int hsd_copy_rows(const void *src, long long sdist, long long soff, long long ncopy, void *dst, long long ddist,
                   long long dlen, int batch)
 {
+    trace(1, src, dst, "copy_rows sdist=%lld soff=%lld ncopy=%lld ddist=%lld dlen=%lld batch=%d", sdist, soff, ncopy, ddist,
+          dlen, batch);
     touch_rows_r((const double *)src + soff, sdist, ncopy, batch, 8);
     touch_rows_w(dst, ddist, dlen, batch, 8);
     return 0;

@@ -1,8 +1,8 @@
 /*
  * sanitize_driver.c -- TEST INFRASTRUCTURE ONLY (tests/test_sanitize_cpu.py).
  *
- * Runs the host C of libhsfft.so (csrc/hsfft_plan.c, hsfft_exec.c, hsfft_real.c,
- * hsfft_convolve.c) against the null device (null_device.c) under
+ * Runs the host C of libhsfft.so (csrc/hsfft_plan.c, hsfft_schedule.c, hsfft_exec.c, hsfft_real.c,
+ * hsfft_convolve.c, hsfft_measure.c, hsfft_crash.c) against the null device (null_device.c) under
  * -fsanitize=address,undefined:
  *   1. planner: fft_init's public fields and twiddle bytes equal the oracle's plan for every
  *      N <= PLAN_MAX and a list of larger sizes (ref highSpeedFFT.c:206-286, :1979-2313);

@@ -111,6 +111,71 @@ def test_c2c_dropin_host_pointers_bit_exact(n):
         assert T.bits_equal(y, oracle_rows(x, sgn)), (n, sgn, T.mismatches(y, oracle_rows(x, sgn)))
 
 
+def _dropin_call(fn, plan_ptr, x, out_dtype, in_dev, out_dev, alias=False):
+    """One drop-in call fn(plan, in, out) with each buffer in host or device memory (alias: one
+    buffer for both).  The output buffer holds stale data before the call.  Returns the output
+    and the input buffer's content after the call."""
+    n = x.size
+    xin = x.copy()
+    stale = np.full(n, -7.25, dtype=out_dtype)
+    bufs = []
+    if in_dev:
+        bufs.append(hsfft.DeviceBuffer.from_array(xin))
+        pin = bufs[-1].ptr
+    else:
+        pin = xin.ctypes.data
+    if alias:
+        pout = pin
+    elif out_dev:
+        bufs.append(hsfft.DeviceBuffer.from_array(stale))
+        pout = bufs[-1].ptr
+    else:
+        pout = stale.ctypes.data
+    fn(plan_ptr, hsfft.VP(pin), hsfft.VP(pout))
+    after = bufs[0].to_array(x.dtype) if in_dev else xin
+    y = after if alias else bufs[-1].to_array(out_dtype) if out_dev else stale
+    for b in bufs:
+        b.free()
+    return y, after
+
+
+def test_dropin_pointer_combinations():
+    """fft_exec, fft_r2c_exec and fft_c2r_exec with every placement of their two buffers -- host /
+    host, device / device, device / host, host / device -- and fft_exec with inp == oup in host
+    and in device memory (the library stages aliased buffers, so the result is the out-of-place
+    one): bit-exact vs the oracle, stale output buffers, inputs left untouched.  fft_exec at
+    N = 1024 (one pass: the small path), 65536 (two passes, the last in place) and 97 (Bluestein);
+    the real pair at N = 4096 and 2^17."""
+    L = hsfft.lib()
+    pairs = [(0, 0), (1, 1), (1, 0), (0, 1)]
+    for n in (1024, 65536, 97):
+        x = T.complex_input(n, T.seed_for(n) ^ 0xD1)
+        want = oracle_rows(x, 1)
+        p = hsfft.Plan(n, 1)
+        for in_dev, out_dev in pairs:
+            y, after = _dropin_call(L.fft_exec, p.ptr, x, np.complex128, in_dev, out_dev)
+            assert T.bits_equal(y, want), ("fft_exec", n, in_dev, out_dev, T.mismatches(y, want))
+            assert T.bits_equal(after, x), ("fft_exec input", n, in_dev, out_dev)
+        for dev in (0, 1):
+            y, _ = _dropin_call(L.fft_exec, p.ptr, x, np.complex128, dev, dev, alias=True)
+            assert T.bits_equal(y, want), ("fft_exec aliased", n, dev, T.mismatches(y, want))
+        p.close()
+    for n in (4096, 1 << 17):
+        x = T.real_input(n, T.seed_for(n) ^ 0xD2)
+        X = T.oracle_r2c(x, 1)
+        back = T.oracle_c2r(X, n, -1)
+        f, iv = hsfft.RealPlan(n, 1), hsfft.RealPlan(n, -1)
+        for in_dev, out_dev in pairs:
+            y, after = _dropin_call(L.fft_r2c_exec, f.ptr, x, np.complex128, in_dev, out_dev)
+            assert T.bits_equal(y, X), ("fft_r2c_exec", n, in_dev, out_dev, T.mismatches(y, X))
+            assert T.bits_equal(after, x), ("fft_r2c_exec input", n, in_dev, out_dev)
+            y, after = _dropin_call(L.fft_c2r_exec, iv.ptr, X, np.float64, in_dev, out_dev)
+            assert T.bits_equal(y, back), ("fft_c2r_exec", n, in_dev, out_dev, T.mismatches(y, back))
+            assert T.bits_equal(after, X), ("fft_c2r_exec input", n, in_dev, out_dev)
+        f.close()
+        iv.close()
+
+
 @pytest.mark.parametrize("n", C2C_SIZES)
 def test_c2c_batched_device_bit_exact(n):
     rows = 3 if n <= 65536 else 1

@@ -166,6 +166,64 @@ def test_12600_runs_as_one_whole_row_pass(monkeypatch):
     assert out.stdout.strip() == "2"
 
 
+SCHEDULES = os.path.join(T.GOLDEN, "schedules.json")
+PIN_SIZES = [8, 1024, 4096, 8192, 1 << 16, 1 << 20, 1 << 21, 1 << 22, 12600, 3000, 5000, 4913, 100000,
+             2288, 22472, 97, 65537, 99991, 131071]
+PIN_KNOB_SIZES = [1 << 20, 1 << 21, 8192, 12600, 100000]
+PIN_KNOBS = ["HSFFT_GENERIC=1", "HSFFT_WHOLE=0", "HSFFT_MR_ROW=0", "HSFFT_PMAX=64", "HSFFT_K1=1", "HSFFT_G1=4",
+             "HSFFT_G2=4"]
+
+
+def plan_debug_lines(plans, knob=None):
+    """The `hsfft plan` lines HSFFT_PLAN_DEBUG=1 prints (stderr) while a fresh process plans
+    every (n, sgn) of `plans` in order, with one optional NAME=VALUE knob set."""
+    code = textwrap.dedent(f"""
+        import sys; sys.path.insert(0, {T.PKG_DIR!r})
+        import hsfft
+        for n, sgn in {list(plans)!r}:
+            p = hsfft.Plan(n, sgn)
+            p.num_passes()
+            p.close()
+    """)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("HSFFT_") or k == "HSFFT_LIB_PATH"}
+    env["HSFFT_PLAN_DEBUG"] = "1"
+    if knob:
+        name, value = knob.split("=")
+        env[name] = value
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stderr.splitlines() if ln.startswith("hsfft plan ")]
+    assert len(lines) == len(plans), (len(lines), len(plans))
+    return lines
+
+
+def record_schedules():
+    """What tests/golden/schedules.json holds: the sha256 of the default-knob sweep N = 2..8192
+    (sgn +1, one line per N, each ended by a newline) and the literal lines of the pinned sizes."""
+    import hashlib
+    sweep = plan_debug_lines([(n, 1) for n in range(2, 8193)])
+    both = [(n, sgn) for n in PIN_SIZES for sgn in (1, -1)]
+    rec = {"sweep_2_8192_sha256": hashlib.sha256("".join(ln + "\n" for ln in sweep).encode()).hexdigest(),
+           "default": dict(zip([f"{n}:{sgn:+d}" for n, sgn in both], plan_debug_lines(both)))}
+    for knob in PIN_KNOBS:
+        rec[knob] = dict(zip([f"{n}:+1" for n in PIN_KNOB_SIZES], plan_debug_lines([(n, 1) for n in PIN_KNOB_SIZES], knob)))
+    return rec
+
+
+def test_pass_schedules_match_recording():
+    """The pass schedule (passes, radix lists, tiles, kernel variants) of every N = 2..8192 and of
+    the headline, odd-radix and Bluestein sizes, with default knobs and under each scheduling
+    knob, is what was recorded in tests/golden/schedules.json: the GPU suite proves outputs, this
+    pins which kernels produce them (no GPU needed to plan).  Re-record with
+    `python tests/test_product_cpu.py` only when a schedule is meant to change."""
+    import json
+    want = json.load(open(SCHEDULES))
+    got = record_schedules()
+    assert sorted(got) == sorted(want)
+    for key in want:
+        assert got[key] == want[key], key
+
+
 @pytest.mark.skipif(os.environ.get("HIP_VISIBLE_DEVICES") is None and hsfft.device_count() > 0,
                     reason="a GPU is present")
 def test_compute_fails_loudly_without_gpu():
@@ -195,3 +253,10 @@ def test_convolve_batched_argument_errors():
     assert L.hsfft_convolve_batched(b"full", b"linear", buf, 8, buf, 3, buf, 0) == 10
     assert L.hsfft_convolve_batched(b"valid", b"linear", buf, 8, buf, 3, buf, 0) == 6
     assert L.hsfft_convolve_batched(b"full", b"circular", buf, 5, buf, 3, buf, 0) == 8
+
+
+if __name__ == "__main__":  # re-record the schedule fixture
+    import json
+    with open(SCHEDULES, "w") as f:
+        json.dump(record_schedules(), f, indent=1, sort_keys=True)
+        f.write("\n")
