@@ -1,6 +1,7 @@
 """Shared helpers for the test-suite: ctypes bindings of the oracle (test infrastructure),
 the compiled reference (oracle/_ref, present only where it was built) and the synthetic
 input generator.  Product bindings live in the package (hsfft)."""
+import collections
 import ctypes
 import hashlib
 import os
@@ -30,6 +31,91 @@ SEEDS = {1: 0x5EED0001, 2: 0x5EED0002, 3: 0x5EED0003, 4: 0x5EED0004, 5: 0x5EED00
 
 def seed_for(n):
     return 0x5EED1000 ^ n
+
+
+# ---------------------------------------------------------------- forced schedules
+# Schedules that only knobs reach, shared by the CPU test that pins them (test_product_cpu.py:
+# pass count, kernel variant and tile of every pass, planned in a fresh process) and the GPU
+# tests that execute them (test_gpu_chunks.py).  `passes` holds one "r=<radix list> A= B= G= Wq="
+# string per pass, as HSFFT_PLAN_DEBUG=1 prints it; `variant` is the v= of every pass (0 the
+# generic LDS kernel, 1 the radix-8 register kernels, 2 the mixed-radix register kernels);
+# `chunks` lists (HSFFT_CHUNK_MB, batch) pairs for the entries whose chain needs scratch, so
+# that the batch is walked in several chunks with a ragged last one.
+ForcedPlan = collections.namedtuple("ForcedPlan", "n env variant passes chunks")
+
+_NO_ROW = {"HSFFT_WHOLE": "0", "HSFFT_MR_ROW": "0"}
+_GEN8 = {"HSFFT_GENERIC": "1", "HSFFT_PMAX": "8"}
+
+FORCED_PLANS = [
+    # three register-kernel passes: a first pass with G = 16, a middle pass with A > 1 and B > 1
+    ForcedPlan(65536, {"HSFFT_K1": "1"}, 1,
+               ("r=2,8 A=4096 B=1 G=16 Wq=1", "r=8,8 A=64 B=16 G=16 Wq=16", "r=8,8 A=1 B=1024 G=32 Wq=32"),
+               ((4, 11), (1, 3))),
+    ForcedPlan(262144, {"HSFFT_K1": "1"}, 1,
+               ("r=8,8 A=4096 B=1 G=16 Wq=1", "r=8,8 A=64 B=64 G=32 Wq=32", "r=8,8 A=1 B=4096 G=32 Wq=32"),
+               ((8, 5),)),
+    # the generic kernel on power-of-two radix lists, one radix per pass
+    ForcedPlan(8192, _GEN8, 0,
+               ("r=2 A=4096 B=1 G=8 Wq=1", "r=8 A=512 B=2 G=8 Wq=2", "r=8 A=64 B=16 G=8 Wq=8",
+                "r=8 A=8 B=128 G=8 Wq=8", "r=8 A=1 B=1024 G=8 Wq=8"),
+               ((1, 19),)),
+    ForcedPlan(32768, _GEN8, 0,
+               ("r=8 A=4096 B=1 G=8 Wq=1", "r=8 A=512 B=8 G=8 Wq=8", "r=8 A=64 B=64 G=8 Wq=8",
+                "r=8 A=8 B=512 G=8 Wq=8", "r=8 A=1 B=4096 G=8 Wq=8"),
+               ()),
+    # mixed radix lists in three generic passes, and one radix per pass
+    ForcedPlan(3000, dict(_NO_ROW, HSFFT_PMAX="64"), 0,
+               ("r=3,5 A=200 B=1 G=8 Wq=1", "r=5,5 A=8 B=15 G=8 Wq=8", "r=8 A=1 B=375 G=8 Wq=8"),
+               ((1, 47),)),
+    ForcedPlan(12600, dict(_NO_ROW, HSFFT_PMAX="64"), 0,
+               ("r=3,3,5 A=280 B=1 G=8 Wq=1", "r=5,7 A=8 B=45 G=8 Wq=8", "r=8 A=1 B=1575 G=8 Wq=8"),
+               ((1, 7),)),
+    ForcedPlan(12600, dict(_NO_ROW, HSFFT_PMAX="8"), 0,
+               ("r=3 A=4200 B=1 G=8 Wq=1", "r=3 A=1400 B=3 G=6 Wq=3", "r=5 A=280 B=9 G=8 Wq=8",
+                "r=5 A=56 B=45 G=8 Wq=8", "r=7 A=8 B=225 G=8 Wq=8", "r=8 A=1 B=1575 G=8 Wq=8"),
+               ((1, 7),)),
+    ForcedPlan(3000, dict(_NO_ROW, HSFFT_PMAX="8"), 0,
+               ("r=3 A=1000 B=1 G=8 Wq=1", "r=5 A=200 B=3 G=6 Wq=3", "r=5 A=40 B=15 G=8 Wq=8",
+                "r=5 A=8 B=75 G=8 Wq=8", "r=8 A=1 B=375 G=8 Wq=8"),
+               ((1, 47),)),
+    # the G1 = 4 first-pass tile and the G2 = 4 / 16 last-pass tiles
+    ForcedPlan(65536, {"HSFFT_G1": "4"}, 1, ("r=2,8,8 A=512 B=1 G=4 Wq=1", "r=8,8,8 A=1 B=128 G=8 Wq=8"), ()),
+    ForcedPlan(262144, {"HSFFT_G1": "4"}, 1, ("r=8,8,8 A=512 B=1 G=4 Wq=1", "r=8,8,8 A=1 B=512 G=8 Wq=8"), ()),
+    ForcedPlan(65536, {"HSFFT_G2": "4"}, 1, ("r=2,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=128 G=4 Wq=4"), ()),
+    ForcedPlan(262144, {"HSFFT_G2": "4"}, 1, ("r=8,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=512 G=4 Wq=4"), ()),
+    ForcedPlan(65536, {"HSFFT_G2": "16"}, 1, ("r=2,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=128 G=16 Wq=16"), ()),
+    ForcedPlan(262144, {"HSFFT_G2": "16"}, 1, ("r=8,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=512 G=16 Wq=16"), ()),
+    # ... which the pipelined [8,8,8] last-pass kernel (pf::k_b512, tiles of 8 columns whatever the
+    # plan says) takes over by default: HSFFT_PF=0 (an execution knob, the plan is the same) leaves
+    # the pass to r8::k_pass<8, 2, G2, G2>, the kernel that has these tiles
+    ForcedPlan(65536, {"HSFFT_G2": "4", "HSFFT_PF": "0"}, 1,
+               ("r=2,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=128 G=4 Wq=4"), ()),
+    ForcedPlan(262144, {"HSFFT_G2": "4", "HSFFT_PF": "0"}, 1,
+               ("r=8,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=512 G=4 Wq=4"), ()),
+    ForcedPlan(65536, {"HSFFT_G2": "16", "HSFFT_PF": "0"}, 1,
+               ("r=2,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=128 G=16 Wq=16"), ()),
+    ForcedPlan(262144, {"HSFFT_G2": "16", "HSFFT_PF": "0"}, 1,
+               ("r=8,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=512 G=16 Wq=16"), ()),
+    # the two-pass schedules of lengths that run as one whole-row pass by default
+    ForcedPlan(4096, {"HSFFT_WHOLE": "0"}, 1, ("r=8,8 A=64 B=1 G=16 Wq=1", "r=8,8 A=1 B=64 G=32 Wq=32"), ()),
+    ForcedPlan(8192, {"HSFFT_WHOLE": "0"}, 1, ("r=2,8 A=512 B=1 G=16 Wq=1", "r=8,8,8 A=1 B=16 G=8 Wq=8"), ()),
+]
+
+# Bluestein lengths by their M-point schedule (default knobs): M = 2^14 and 2^17 run the chains
+# of run_bluestein (the inverse chain stores through the chirp, so it needs scratch), M = 2^18 the
+# three-launch path under HSFFT_BLUE_XCD=0.  chunks: (HSFFT_BLUE_CHUNK_MB, HSFFT_CHUNK_MB, batch).
+BLUESTEIN_PLANS = [
+    ForcedPlan(5003, {}, 1, ("r=4,8 A=512 B=1 G=32 Wq=1", "r=8,8,8 A=1 B=32 G=8 Wq=8"), ((2, 1, 11),)),
+    ForcedPlan(40009, {}, 1, ("r=4,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=256 G=8 Wq=8"), ((8, 4, 7),)),
+    ForcedPlan(99991, {}, 1, ("r=8,8,8 A=512 B=1 G=8 Wq=1", "r=8,8,8 A=1 B=512 G=8 Wq=8"), ((8, None, 5),)),
+]
+BLUESTEIN_M = {5003: 1 << 14, 40009: 1 << 17, 99991: 1 << 18}
+
+
+def rows_per_chunk(chunk_mb, m, elem=16):
+    """rows of m elements (16-byte complex by default) per chunk of a HSFFT_*CHUNK_MB knob: the
+    chunk is max(1 MiB, knob) bytes and holds at least one row"""
+    return max(1, max(1 << 20, int(chunk_mb * (1 << 20))) // (elem * m))
 
 
 def _bind(lib, name, restype, argtypes):

@@ -176,7 +176,8 @@ PIN_KNOBS = ["HSFFT_GENERIC=1", "HSFFT_WHOLE=0", "HSFFT_MR_ROW=0", "HSFFT_PMAX=6
 
 def plan_debug_lines(plans, knob=None):
     """The `hsfft plan` lines HSFFT_PLAN_DEBUG=1 prints (stderr) while a fresh process plans
-    every (n, sgn) of `plans` in order, with one optional NAME=VALUE knob set."""
+    every (n, sgn) of `plans` in order, with optional knobs set: one NAME=VALUE string or a
+    dict of several."""
     code = textwrap.dedent(f"""
         import sys; sys.path.insert(0, {T.PKG_DIR!r})
         import hsfft
@@ -187,7 +188,9 @@ def plan_debug_lines(plans, knob=None):
     """)
     env = {k: v for k, v in os.environ.items() if not k.startswith("HSFFT_") or k == "HSFFT_LIB_PATH"}
     env["HSFFT_PLAN_DEBUG"] = "1"
-    if knob:
+    if isinstance(knob, dict):
+        env.update(knob)
+    elif knob:
         name, value = knob.split("=")
         env[name] = value
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
@@ -222,6 +225,38 @@ def test_pass_schedules_match_recording():
     assert sorted(got) == sorted(want)
     for key in want:
         assert got[key] == want[key], key
+
+
+PASS_RE = re.compile(r"\[P=(\d+) (r=[\d,]+ A=\d+ B=\d+ G=\d+ Wq=\d+) v=(\d+)\]")
+
+
+def test_forced_plans_table():
+    """Every entry of hsfft_testlib.FORCED_PLANS and BLUESTEIN_PLANS -- the schedules the GPU
+    chunk tests (test_gpu_chunks.py) force with knobs -- plans, in a fresh process with exactly
+    the entry's knobs and for both signs, to the passes the table records: their number, the
+    radix list and tile of each, and the kernel variant of every pass.  A renamed or re-read
+    knob thus fails here instead of quietly turning a GPU test into a one-pass, one-chunk run
+    of the default schedule.  (No GPU needed to plan.)"""
+    table = T.FORCED_PLANS + T.BLUESTEIN_PLANS
+    assert len(table) == len({(fp.n, tuple(sorted(fp.env.items()))) for fp in table})  # no entry twice
+    by_env = {}
+    for fp in table:
+        by_env.setdefault(tuple(sorted(fp.env.items())), []).append(fp)
+    for env, fps in by_env.items():
+        plans = [(fp.n, sgn) for fp in fps for sgn in (1, -1)]
+        lines = plan_debug_lines(plans, dict(env))
+        for (n, sgn), line in zip(plans, lines):
+            fp = next(f for f in fps if f.n == n)
+            m = T.BLUESTEIN_M.get(n, n)
+            assert line.startswith(f"hsfft plan N={n} M={m}:"), (n, env, line)
+            got = PASS_RE.findall(line)
+            assert len(got) == line.count("[") == len(fp.passes), (n, sgn, env, line)
+            for i, (P, shape, v) in enumerate(got):
+                assert shape == fp.passes[i], (n, sgn, env, i, line)
+                assert int(v) == fp.variant, (n, sgn, env, i, line)
+                assert int(P) == np.prod([int(r) for r in shape.split()[0][2:].split(",")]), (n, i, line)
+            if fp.chunks and fp in T.FORCED_PLANS:
+                assert len(fp.passes) >= 3  # only a chain of three or more passes needs scratch
 
 
 @pytest.mark.skipif(os.environ.get("HIP_VISIBLE_DEVICES") is None and hsfft.device_count() > 0,
