@@ -212,6 +212,166 @@ def real_input(n, seed, batch=1, row0=0):
     return x.reshape(batch, n) if batch > 1 else x
 
 
+# ---------------------------------------------------------------- special-value inputs
+# Rows on which arithmetic that is invisible on dense random data shows: exact zeros of either
+# sign (a twiddle multiply skipped or not skipped at k = 0, a - b against -(b - a)), subnormals
+# and the range just under overflow.  Every kind is finite.
+SPECIAL_KINDS = ("const", "alt", "comb4", "negzero", "zfield", "impulse", "realonly", "tiny", "huge")
+
+
+def _smallest_prime_factor(n):
+    f = 2
+    while f * f <= n:
+        if n % f == 0:
+            return f
+        f += 1
+    return n
+
+
+def special_inputs(n, kind, seed):
+    """one complex row of length n of the given kind (SPECIAL_KINDS)"""
+    j = np.arange(n)
+    re, im = np.zeros(n), np.zeros(n)
+    if kind == "const":
+        re[:], im[:] = 1.0, -0.5
+    elif kind == "alt":  # +1+0j, -1-0j, ...
+        re[:] = np.where(j % 2 == 0, 1.0, -1.0)
+        im[:] = np.where(j % 2 == 0, 0.0, -0.0)
+    elif kind == "comb4":  # period 4, or the smallest prime factor where 4 does not divide n
+        per = 4 if n % 4 == 0 else _smallest_prime_factor(n)
+        re[:] = np.where(j % per == 0, 0.75, -0.0)
+        im[:] = np.where(j % per == 0, -0.25, 0.0)
+    elif kind == "negzero":
+        re[:], im[:] = -0.0, -0.0
+    elif kind == "zfield":  # every word +0 or -0 at random
+        u = splitmix_uniform(seed, np.arange(2 * n, dtype=np.uint64))
+        re[:] = np.where(u[0::2] < 0, -0.0, 0.0)
+        im[:] = np.where(u[1::2] < 0, -0.0, 0.0)
+    elif kind == "impulse":  # -1 at index 1 (real part), +1 at index n-1 (imaginary part)
+        re[1 % n] = -1.0
+        im[n - 1] = 1.0
+    elif kind == "realonly":
+        re[:] = complex_input(n, seed).real
+        im[:] = np.where(j % 3 == 0, -0.0, 0.0)
+    elif kind == "tiny":  # subnormal inputs and subnormal / small normal outputs
+        return complex_input(n, seed) * 2.0 ** -1040
+    elif kind == "huge":
+        return complex_input(n, seed) * 2.0 ** 1000
+    else:
+        raise ValueError(kind)
+    x = np.empty(n, dtype=np.complex128)
+    x.real, x.imag = re, im
+    return x
+
+
+def special_real(n, kind, seed):
+    """the real part of special_inputs(n, kind, seed): the real variant for r2c and convolve"""
+    return np.ascontiguousarray(special_inputs(n, kind, seed).real)
+
+
+def special_rows(n, kinds, seed, real=False):
+    """one row per kind, row r under seed + r"""
+    f = special_real if real else special_inputs
+    return np.stack([f(n, k, seed + r) for r, k in enumerate(kinds)])
+
+
+def nan_words(a):
+    """the 8-byte words of a that are NaN by class: exponent all ones, mantissa non-zero"""
+    w = np.ascontiguousarray(a).view(np.uint64).reshape(-1)
+    return ((w >> np.uint64(52)) & np.uint64(0x7FF) == np.uint64(0x7FF)) & (w & np.uint64((1 << 52) - 1) != np.uint64(0))
+
+
+def same_bits_nan_aware(a, b):
+    """bit equality outside NaN words: the NaN positions coincide (sign and payload of a NaN
+    differ between x86 and the GPU) and every other word -- zeros and infinities with their
+    sign included -- is bit-equal.  The suite's only relaxation of bits_equal, for the
+    non-finite inputs alone."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    na, nb = nan_words(a), nan_words(b)
+    if not np.array_equal(na, nb):
+        return False
+    wa, wb = a.view(np.uint64).reshape(-1), b.view(np.uint64).reshape(-1)
+    return bool(np.array_equal(wa[~na], wb[~na]))
+
+
+def zero_words(a):
+    """count of 8-byte words of a that are an exact zero of either sign"""
+    w = np.ascontiguousarray(a).view(np.uint64)
+    return int(np.count_nonzero(w << np.uint64(1) == np.uint64(0)))
+
+
+def first_diff(a, b):
+    """index of the first differing 8-byte word, or -1"""
+    d = np.flatnonzero(np.ascontiguousarray(a).view(np.uint64).reshape(-1) !=
+                       np.ascontiguousarray(b).view(np.uint64).reshape(-1))
+    return int(d[0]) if d.size else -1
+
+
+# Lengths at which the structured kinds are pinned to give mostly exact zeros (powers of two
+# and 12600), and the non-finite cases: the index of the one infinite element, the first of
+# (n//3, n//2, 1, n-1) at which the oracle's output is between 1 % and 99 % NaN words for
+# +Inf in the real part and for -Inf in the imaginary part, both signs.  N = 8 has no such
+# index (a single radix-8 butterfly adds and subtracts only: Inf without NaN, or, with the
+# sqrt(1/2) multiplies, no partial mix), so it is not in the table.  test_special_cpu.py pins
+# all of this from the oracle alone.
+ZERO_RICH_SIZES = (512, 4096, 65536, 12600)
+NONFINITE_CANDIDATES = ("n//3", "n//2", "1", "n-1")
+NONFINITE_INDEX = {12: 6, 20: 6, 28: 9, 60: 30, 64: 21, 100: 33, 512: 170, 1000: 333, 12600: 1}
+NONFINITE_LEFT_OUT = (8,)
+
+
+def nonfinite_candidates(n):
+    return (n // 3, n // 2, 1, n - 1)
+
+
+def skip_probe_index(n):
+    """The index at which one infinite element tells a combine stage that skips its k = 0 twiddle
+    from one that multiplies, or 0 where there is none (Bluestein lengths; plans without a
+    radix-4/5/7 combine).  The recursion splits index j by its mixed-radix digits, outermost
+    factor first; the element with digit d in a stage enters that stage's k = 0 butterfly in
+    branch d, and branches >= 1 are the ones a twiddle multiplies.  Digit 1 in every radix-4/5/7
+    combine stage and digit 0 in every other stage (which multiply by (1, 0) even at k = 0, and
+    would turn the Inf into NaN before it reaches a skipping stage) brings a clean Inf to each
+    skipped multiply: the oracle keeps Inf words there, a kernel that multiplies makes them NaN."""
+    _, fac, lt, _ = oracle_plan_twiddles(n, 1)
+    if lt:
+        return 0
+    idx, stride = 0, 1
+    for r in fac[:-1]:  # the last factor is the leaf: no twiddles
+        if r in (4, 5, 7):
+            idx += stride
+        stride *= r
+    return idx
+
+
+def inf_words(a):
+    return int(np.count_nonzero(np.isinf(np.ascontiguousarray(a).view(np.float64))))
+
+
+def nonfinite_rows(n, idx, seed):
+    """three dense rows: +Inf in the real part at idx, -Inf in the imaginary part at idx, and a
+    finite one"""
+    x = complex_input(n, seed, batch=3).reshape(3, n)
+    x[0, idx] = complex(np.inf, x[0, idx].imag)
+    x[1, idx] = complex(x[1, idx].real, -np.inf)
+    return x
+
+
+def nan_fraction(a):
+    return float(nan_words(a).mean())
+
+
+def oracle_convolve(typ, ct, a, b):
+    """orc_convolve of one pair of real rows: the output row"""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    o = np.zeros(4 * (a.size + b.size) + 8)
+    ln = oracle().orc_convolve(typ, ct, ptr(a), a.size, ptr(b), b.size, ptr(o), 0)
+    assert ln > 0, (typ, ct, a.size, b.size, ln)
+    return o[:ln].copy()
+
+
 # ---------------------------------------------------------------- oracle conveniences
 def oracle_c2c(x, sgn, flags=0, out_init=None):
     lib = oracle()
