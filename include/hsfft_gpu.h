@@ -41,7 +41,8 @@ int hsfft_synchronize(void);
  * convolution buffers) after waiting for queued work; the pool regrows on demand.  The pool
  * otherwise persists for the process: up to the largest chunk a call needed (c2c chains
  * HSFFT_CHUNK_MB, default 256 MiB x 2; Bluestein HSFFT_BLUE_CHUNK_MB, 4 GiB x 2; real paths
- * HSFFT_REAL_CHUNK_MB, 16 GiB -- each halved while allocation fails). */
+ * HSFFT_REAL_CHUNK_MB, 16 GiB; the 2D paths HSFFT_2D_CHUNK_MB, 1 GiB -- each halved while
+ * allocation fails). */
 int hsfft_release_scratch(void);
 /* Teardown: waits for every device's work, then releases every device object the library
  * holds on every device -- scratch pool, page-locked staging slots, the device state of every
@@ -90,6 +91,31 @@ int hsfft_c2r_batched(fft_real_object obj, const fft_data *d_in, fft_type *d_out
 int hsfft_convolve_batched(const char *type, const char *conv_type, const fft_type *d_a,
                            int length1, const fft_type *d_b, int length2, fft_type *d_out,
                            int batch);
+
+/* --- transforms along other axes: transpose, 2D, columns -------------------------------- */
+/* All three are asynchronous on the library stream and run under the device lock, like
+ * hsfft_exec_batched; Bluestein lengths keep that call's error-word contract (below).  They
+ * return HSFFT_ERR_ARG -- before any device is touched -- for NULL pointers, d_in == d_out or
+ * input and output ranges that overlap, a negative batch or a dimension < 1; batch == 0 returns
+ * 0.  d_in is never written.
+ * hsfft_exec_2d and hsfft_exec_columns keep one scratch buffer in the library's pool (freed by
+ * hsfft_release_scratch / hsfft_finalize): HSFFT_2D_CHUNK_MB (default 1024 MiB, at least 1)
+ * bounds it, and a call walks its batch in chunks of whole images -- as many as fit, at least
+ * one (hsfft_exec_columns holds two copies of a chunk, so half as many fit), halved while the
+ * allocation fails. */
+/* out[b][c][r] = in[b][r][c]; d_in != d_out, ranges must not overlap.  A pure copy of 16-byte
+ * elements: every word, NaN payloads included, arrives unchanged. */
+int hsfft_transpose_batched(const fft_data *d_in, fft_data *d_out, int rows, int cols, int batch);
+/* 2D c2c of batch row-major images of p0->N rows by p1->N columns: the 1D transform of p1 on every
+ * row, then the 1D transform of p0 on every column of that result (this order is part of the
+ * contract: results are bit-identical to the reference's fft_exec applied that way). No scaling.
+ * p0 and p1 may be one plan (square images) and may differ in sign: each is applied as planned.
+ * Four trips through HBM per chunk: rows, transpose, rows (the columns), transpose. */
+int hsfft_exec_2d(fft_object p0, fft_object p1, const fft_data *d_in, fft_data *d_out, int batch);
+/* 1D c2c along axis 0 of batch row-major matrices of p->N rows by ncols columns (out[b][k][c] =
+ * the transform over r of in[b][r][c]).  Three trips through HBM per chunk: transpose, rows,
+ * transpose. */
+int hsfft_exec_columns(fft_object p, const fft_data *d_in, fft_data *d_out, int ncols, int batch);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */

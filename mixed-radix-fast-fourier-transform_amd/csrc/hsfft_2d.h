@@ -1,0 +1,264 @@
+/*
+ * hsfft_2d.h -- batched transpose of 16-byte elements and the 2D / column c2c drivers built on it
+ * (hsfft_transpose_batched, hsfft_exec_2d, hsfft_exec_columns of include/hsfft_gpu.h; the
+ * reference has no counterpart).  Included at the end of hsfft_device.hip: the drivers launch
+ * the transpose directly, so no host C file needs a new device-layer symbol.
+ *
+ * The 1D transforms are hs_c2c_rows() unchanged -- every planned length over contiguous rows --
+ * and a transpose is a pure copy, so a 2D result is, word for word, the reference's fft_exec
+ * applied to every row and then to every column of that result.
+ */
+#include "hsfft_gpu.h"
+#include "hsfft_host.h"
+
+namespace tr2d {
+
+/* out[b][c][r] = in[b][r][c] for one TS x TS tile per workgroup of 256 threads.
+ *
+ * Both global sides are 16 B per lane with lanes on consecutive elements of the side's fastest
+ * axis: TS = 32 gives two 512-B runs per wave-instruction, TS = 64 one 1-KiB run.  The tile is
+ * staged through LDS with a row pitch of TS + 1 elements.  The row-wise stores (ds_write_b128,
+ * 8 contiguous lanes per group, banks modulo 32 dwords) cover 128 contiguous bytes per group:
+ * conflict-free at any pitch.  The column-wise loads (ds_read_b128, banks modulo 64 dwords = 16
+ * slots of 16 B, groups of 16 lanes {0-3,12-15,20-27}, ...) put lane l at slot (l * (TS + 1) +
+ * const) mod 16 = (l + const) mod 16, and every group holds 16 distinct l mod 16: conflict-free.
+ * At pitch TS the 16 lanes of a group would all sit on one slot (16-way).
+ *
+ * The batch is flattened into the 1D grid (tile index = (b * ntr + tr) * ntc + tc, 64-bit
+ * arithmetic throughout); DIAG rotates the tile column by the tile row, so that workgroups that
+ * run together differ in both coordinates and neither side walks one power-of-two stride
+ * (+7 % on 32768 x 512, -11 % on square images; off by default).
+ * No arithmetic on the data: plain 16-B vector loads and stores, every word copied verbatim. */
+template <int TS, bool DIAG>
+__global__ __launch_bounds__(256) void k_transpose(const v2d *__restrict__ in, v2d *__restrict__ out, long long rows,
+                                                   long long cols, long long ntr, long long ntc, long long tile0)
+{
+    extern __shared__ v2d tr_tile[];
+    constexpr int P = TS + 1, RY = 256 / TS, NK = TS / RY;
+    const long long t = tile0 + blockIdx.x, per = ntr * ntc;
+    const long long b = t / per, rem = t - b * per;
+    const long long tr = rem / ntc;
+    long long tc = rem - tr * ntc;
+    if (DIAG) {
+        tc += tr % ntc;
+        if (tc >= ntc) tc -= ntc;
+    }
+    const int tx = threadIdx.x % TS, ty = threadIdx.x / TS;
+    const long long r0 = tr * TS, c0 = tc * TS;
+    const v2d *src = in + b * rows * cols;
+    v2d *dst = out + b * rows * cols;
+    v2d v[NK];
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long r = r0 + ty + k * RY, c = c0 + tx;
+        if (r < rows && c < cols) v[k] = src[r * cols + c];
+    }
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long r = r0 + ty + k * RY, c = c0 + tx;
+        if (r < rows && c < cols) tr_tile[(ty + k * RY) * P + tx] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long c = c0 + ty + k * RY, r = r0 + tx; /* output row c, output column r */
+        if (c < cols && r < rows) dst[c * rows + r] = tr_tile[tx * P + ty + k * RY];
+    }
+}
+
+/* tiles per launch: the grid's x dimension is 32-bit */
+constexpr long long MAX_GRID = 1LL << 30;
+
+/* (device lock held by the caller) queue the transposes of `batch` images on the selected stream */
+static int launch(const void *in, void *out, long long rows, long long cols, long long batch)
+{
+    typedef void (*kfn)(const v2d *, v2d *, long long, long long, long long, long long, long long);
+    /* HSFFT_TR_TILE (64 | 32) and HSFFT_TR_DIAG (0 | 1): measurement knobs, the four variants of
+     * DESIGN.md §8's table (tools/bench_2d.py --variants); the defaults are the fastest there */
+    const int ts = hs_env_int("HSFFT_TR_TILE", 64) == 32 ? 32 : 64;
+    const int diag = hs_env_int("HSFFT_TR_DIAG", 0) != 0;
+    const kfn fn = ts == 64 ? (diag ? k_transpose<64, true> : k_transpose<64, false>)
+                            : (diag ? k_transpose<32, true> : k_transpose<32, false>);
+    const size_t lds = (size_t)ts * (ts + 1) * sizeof(v2d);
+    const long long ntr = (rows + ts - 1) / ts, ntc = (cols + ts - 1) / ts;
+    if (ntr > MAX_GRID / ntc) {
+        snprintf(g_err, sizeof g_err, "transpose: %lld x %lld tiles per image", ntr, ntc);
+        return -1;
+    }
+    if (lds > 65536) { /* once per device and kernel (callers hold the device lock) */
+        static bool lds_set[HS_MAX_DEV][2];
+        bool &done = lds_set[cur_dev()][diag];
+        if (!done) HCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    const long long total = batch * ntr * ntc;
+    for (long long t0 = 0; t0 < total; t0 += MAX_GRID) {
+        const long long g = total - t0 < MAX_GRID ? total - t0 : MAX_GRID;
+        hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(256), lds, stream(), (const v2d *)in, (v2d *)out, rows, cols, ntr,
+                           ntc, t0);
+        HCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+static int transpose(const void *in, void *out, long long rows, long long cols, long long batch)
+{
+    const int rc = launch(in, out, rows, cols, batch);
+    if (rc) hs_seterr("transpose: %s", g_err);
+    return rc ? HSFFT_ERR_DEVICE : 0;
+}
+
+/* Scratch of the 2D paths (HS_SCR_2D): HSFFT_2D_CHUNK_MB (default 1024) bounds it.  A call walks
+ * its batch in chunks of whole images: bytes / (copies * image bytes) images, at least one, at
+ * most the batch and at most what keeps a chunk's row count an int; halved while the allocation
+ * fails; the last chunk may be ragged.  hsfft_exec_2d needs one copy of the chunk, and
+ * hsfft_exec_columns two. */
+static void *chunk_scratch(long long img_elems, int max_dim, int copies, int batch, long long *per_chunk)
+{
+    const size_t img_bytes = sizeof(fft_data) * (size_t)img_elems;
+    long long ci = (long long)(hs_env_mb("HSFFT_2D_CHUNK_MB", 1024.0) / ((size_t)copies * img_bytes));
+    if (ci > batch) ci = batch;
+    if (ci > 0x7fffffffLL / max_dim) ci = 0x7fffffffLL / max_dim;
+    if (ci < 1) ci = 1;
+    void *S;
+    for (;;) {
+        S = hs_scratch(HS_SCR_2D, (size_t)copies * img_bytes * (size_t)ci);
+        if (S || ci == 1) break;
+        ci = (ci + 1) / 2;
+    }
+    if (!S) hs_seterr("2D scratch allocation of %lld bytes failed", (long long)copies * (long long)img_bytes * ci);
+    *per_chunk = ci;
+    return S;
+}
+
+/* `count` contiguous rows of e's length; a length-1 transform is a copy (ref :332-342), queued
+ * here as one copy instead of hs_c2c_rows' one per row */
+static int rows(hs_entry *e, const fft_data *in, fft_data *out, long long count)
+{
+    if (e->N > 1) return hs_c2c_rows(e, in, e->N, out, e->N, (int)count);
+    if (hsd_d2d_async(out, in, sizeof(fft_data) * (size_t)count)) {
+        hs_seterr("2D copy: %s", hsd_errstr());
+        return HSFFT_ERR_DEVICE;
+    }
+    return 0;
+}
+
+/* (device lock held) rows of p1 then columns of p0 of `batch` n0 x n1 images, per chunk:
+ * rows in -> S, transpose S -> out, rows out -> S (the columns, now contiguous), transpose
+ * S -> out.  d_in is only read. */
+static int exec_2d(hs_entry *e0, hs_entry *e1, const fft_data *in, fft_data *out, int batch)
+{
+    const long long n0 = e0->N, n1 = e1->N, img = n0 * n1;
+    if (img > (1LL << 40)) {
+        hs_seterr("hsfft_exec_2d: image of %lld x %lld samples is too large", n0, n1);
+        return HSFFT_ERR_ARG;
+    }
+    long long ci;
+    fft_data *S = (fft_data *)chunk_scratch(img, (int)(n0 > n1 ? n0 : n1), 1, batch, &ci);
+    if (!S) return HSFFT_ERR_NOMEM;
+    for (long long b0 = 0; b0 < batch; b0 += ci) {
+        const long long cb = batch - b0 < ci ? batch - b0 : ci;
+        const fft_data *ib = in + b0 * img;
+        fft_data *ob = out + b0 * img;
+        int rc = rows(e1, ib, S, cb * n0);
+        if (!rc) rc = transpose(S, ob, n0, n1, cb);
+        if (!rc) rc = rows(e0, ob, S, cb * n1);
+        if (!rc) rc = transpose(S, ob, n1, n0, cb);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+/* (device lock held) the transform of p along axis 0 of `batch` n x ncols matrices, per chunk:
+ * transpose in -> S0, rows S0 -> S1, transpose S1 -> out.  Three trips through HBM with two
+ * chunk-sized halves of the scratch; with one half the second transpose would have to land in
+ * the scratch again (its source is the output buffer) and a fourth trip, a copy, would follow. */
+static int exec_columns(hs_entry *e, const fft_data *in, fft_data *out, int ncols, int batch)
+{
+    const long long n = e->N, img = n * (long long)ncols;
+    if (img > (1LL << 40)) {
+        hs_seterr("hsfft_exec_columns: matrix of %lld x %d samples is too large", n, ncols);
+        return HSFFT_ERR_ARG;
+    }
+    long long ci;
+    fft_data *S0 = (fft_data *)chunk_scratch(img, (int)(n > ncols ? n : ncols), 2, batch, &ci);
+    if (!S0) return HSFFT_ERR_NOMEM;
+    fft_data *S1 = S0 + ci * img;
+    for (long long b0 = 0; b0 < batch; b0 += ci) {
+        const long long cb = batch - b0 < ci ? batch - b0 : ci;
+        int rc = transpose(in + b0 * img, S0, n, ncols, cb);
+        if (!rc) rc = rows(e, S0, S1, cb * ncols);
+        if (!rc) rc = transpose(S1, out + b0 * img, ncols, n, cb);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+/* the byte ranges [a, a + n) and [b, b + n) share a byte */
+static bool overlap(const void *a, const void *b, long long elems)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, n = (uintptr_t)elems * sizeof(fft_data);
+    return pa < pb ? pb - pa < n : pa - pb < n;
+}
+
+}  // namespace tr2d
+
+extern "C" {
+
+int hsfft_transpose_batched(const fft_data *d_in, fft_data *d_out, int rows, int cols, int batch)
+{
+    hs_seterr("%s", "");
+    if (!d_in || !d_out || d_in == d_out || batch < 0 || rows < 1 || cols < 1 ||
+        tr2d::overlap(d_in, d_out, (long long)rows * cols * batch)) {
+        hs_seterr("hsfft_transpose_batched: invalid arguments");
+        return HSFFT_ERR_ARG;
+    }
+    if (batch == 0) return 0;
+    int rc = hs_require_gpu();
+    if (rc) return rc;
+    const int d = hs_lock_device();
+    rc = tr2d::transpose(d_in, d_out, rows, cols, batch);
+    hs_unlock_device(d);
+    return rc;
+}
+
+int hsfft_exec_2d(fft_object p0, fft_object p1, const fft_data *d_in, fft_data *d_out, int batch)
+{
+    hs_seterr("%s", "");
+    if (!p0 || !p1 || !d_in || !d_out || d_in == d_out || batch < 0 || p0->N < 1 || p1->N < 1 ||
+        tr2d::overlap(d_in, d_out, (long long)p0->N * p1->N * batch)) {
+        hs_seterr("hsfft_exec_2d: invalid arguments");
+        return HSFFT_ERR_ARG;
+    }
+    if (batch == 0) return 0;
+    int rc = hs_require_gpu();
+    if (rc) return rc;
+    const int d = hs_lock_device();
+    hs_entry *e0 = hs_entry_get(p0), *e1 = hs_entry_get(p1);
+    rc = e0 && e1 ? tr2d::exec_2d(e0, e1, d_in, d_out, batch) : HSFFT_ERR_ARG;
+    hs_entry_put(e1);
+    hs_entry_put(e0);
+    hs_unlock_device(d);
+    return rc;
+}
+
+int hsfft_exec_columns(fft_object p, const fft_data *d_in, fft_data *d_out, int ncols, int batch)
+{
+    hs_seterr("%s", "");
+    if (!p || !d_in || !d_out || d_in == d_out || batch < 0 || ncols < 1 || p->N < 1 ||
+        tr2d::overlap(d_in, d_out, (long long)p->N * ncols * batch)) {
+        hs_seterr("hsfft_exec_columns: invalid arguments");
+        return HSFFT_ERR_ARG;
+    }
+    if (batch == 0) return 0;
+    int rc = hs_require_gpu();
+    if (rc) return rc;
+    const int d = hs_lock_device();
+    hs_entry *e = hs_entry_get(p);
+    rc = e ? tr2d::exec_columns(e, d_in, d_out, ncols, batch) : HSFFT_ERR_ARG;
+    hs_entry_put(e);
+    hs_unlock_device(d);
+    return rc;
+}
+
+}  // extern "C"

@@ -9,6 +9,8 @@
  *   k_fill_*       : splitmix64 synthetic inputs (bench / tests).
  *   k_r2c_post / k_c2r_pre : real-signal split / merge (ref src/real.c:108-132, :169-179).
  *   k_cmul / k_scale_real / k_copy_rows : convolution helpers (ref src/convolve.c:137-160).
+ *   k_transpose    : hsfft_2d.h -- tiled transpose of 16-byte elements, with the 2D / column
+ *                    drivers that launch it between hs_c2c_rows() calls.
  *
  * Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (no FMA contraction: the results
  * must be bit-identical to the reference's separately rounded multiplies and adds).
@@ -1539,3 +1541,5 @@ int hsd_pass_timer_read(int n, float *ms)
 }
 
 }  // extern "C"
+
+#include "hsfft_2d.h"

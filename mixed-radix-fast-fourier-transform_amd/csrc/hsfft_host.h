@@ -115,7 +115,10 @@ enum {
     HS_SCR_BLUE_MID2 = 8, /* Bluestein second intermediate (fused middle kernel) */
     HS_SCR_HOST_OUT = 9,  /* hsfft_exec_batched_host: two download slots */
     HS_SCR_CONV_SPEC = 10,/* convolution: both compact spectra */
-    HS_NSCRATCH = 11
+    HS_SCR_2D = 11,       /* hsfft_exec_2d / hsfft_exec_columns (hsfft_2d.h): the chunk between the row
+                           * transforms and the transposes; a class of its own, because the row
+                           * transforms in between use the chain and Bluestein classes */
+    HS_NSCRATCH = 12
 };
 void *hs_scratch(int cls, size_t bytes);
 /* Staging of the drop-in entry points (device lock held).  Caller buffers are used directly

@@ -60,6 +60,9 @@ SIGNATURES = {
     "hsfft_r2c_batched_compact": (CI, [VP, VP, VP, CI]),
     "hsfft_c2r_batched": (CI, [VP, VP, VP, CI]),
     "hsfft_convolve_batched": (CI, [ctypes.c_char_p, ctypes.c_char_p, VP, CI, VP, CI, VP, CI]),
+    "hsfft_transpose_batched": (CI, [VP, VP, CI, CI, CI]),
+    "hsfft_exec_2d": (CI, [VP, VP, VP, VP, CI]),
+    "hsfft_exec_columns": (CI, [VP, VP, VP, CI, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -244,6 +247,49 @@ def exec_batched_host(plan, x, out=None):
     batch = x.shape[0] if x.ndim == 2 else 1
     check(lib().hsfft_exec_batched_host(plan.ptr, _ptr(x), _ptr(out), batch), "exec_batched_host")
     return out
+
+
+def transpose_batched(d_in, d_out, rows, cols, batch):
+    """out[b][c][r] = in[b][r][c] for batch matrices of rows x cols 16-byte elements"""
+    return check(lib().hsfft_transpose_batched(VP(d_in.ptr), VP(d_out.ptr), rows, cols, batch), "transpose_batched")
+
+
+def exec_2d(plan0, plan1, d_in, d_out, batch):
+    """2D c2c of batch images of plan0.n rows x plan1.n columns: plan1 on the rows, then plan0 on the columns"""
+    return check(lib().hsfft_exec_2d(plan0.ptr, plan1.ptr, VP(d_in.ptr), VP(d_out.ptr), batch), "exec_2d")
+
+
+def exec_columns(plan, d_in, d_out, ncols, batch):
+    """c2c along axis 0 of batch matrices of plan.n rows x ncols columns"""
+    return check(lib().hsfft_exec_columns(plan.ptr, VP(d_in.ptr), VP(d_out.ptr), ncols, batch), "exec_columns")
+
+
+def fft2(x, sgn=1):
+    """2D c2c over the last two axes of a complex128 array of shape (..., n0, n1), unscaled:
+    plans, uploads, runs hsfft_exec_2d and downloads"""
+    x = np.ascontiguousarray(x, dtype=np.complex128)
+    if x.ndim < 2:
+        raise ValueError("fft2 needs an array of at least two dimensions")
+    n0, n1 = x.shape[-2:]
+    if x.size == 0:
+        return np.empty_like(x)
+    batch = x.size // (n0 * n1)
+    made = []
+    try:
+        p0 = Plan(n0, sgn)
+        made.append(p0.close)
+        p1 = p0 if n1 == n0 else Plan(n1, sgn)
+        made.append(p1.close)
+        d_in = DeviceBuffer.from_array(x)
+        made.append(d_in.free)
+        d_out = DeviceBuffer(x.nbytes)
+        made.append(d_out.free)
+        exec_2d(p0, p1, d_in, d_out, batch)
+        synchronize()
+        return d_out.to_array(np.complex128).reshape(x.shape)
+    finally:
+        for release in reversed(made):
+            release()
 
 
 def r2c_batched(rplan, d_in, d_out, batch):
