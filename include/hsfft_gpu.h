@@ -41,7 +41,8 @@ int hsfft_synchronize(void);
  * convolution buffers) after waiting for queued work; the pool regrows on demand.  The pool
  * otherwise persists for the process: up to the largest chunk a call needed (c2c chains
  * HSFFT_CHUNK_MB, default 256 MiB x 2; Bluestein HSFFT_BLUE_CHUNK_MB, 4 GiB x 2; real paths
- * HSFFT_REAL_CHUNK_MB, 16 GiB; the 2D paths HSFFT_2D_CHUNK_MB, 1 GiB -- each halved while
+ * HSFFT_REAL_CHUNK_MB, 16 GiB; the 2D paths, complex and real, HSFFT_2D_CHUNK_MB, 1 GiB -- the
+ * real 2D transforms hold that and the real paths' buffer together -- each halved while
  * allocation fails). */
 int hsfft_release_scratch(void);
 /* Teardown: waits for every device's work, then releases every device object the library
@@ -116,6 +117,31 @@ int hsfft_exec_2d(fft_object p0, fft_object p1, const fft_data *d_in, fft_data *
  * the transform over r of in[b][r][c]).  Three trips through HBM per chunk: transpose, rows,
  * transpose. */
 int hsfft_exec_columns(fft_object p, const fft_data *d_in, fft_data *d_out, int ncols, int batch);
+/* 2D transforms of real images.  In all three, r1 = fft_real_init(n1, s1) with n1 even is the real
+ * plan of the rows, p0 (n0 = p0->N >= 1, any planned length) the plan of the columns, and a "half
+ * spectrum" is n0 rows of n1/2+1 bins (row pitch n1/2+1).  Same conventions as above: asynchronous
+ * under the device lock, the Bluestein error-word contract of hsfft_exec_batched, d_in never
+ * written, no scaling.  HSFFT_ERR_ARG -- before any device is touched -- for NULL plans or
+ * pointers, d_in == d_out or input and output byte ranges that overlap (each range with its own
+ * element size and count), a negative batch; batch == 0 returns 0.  Scratch as above, with the
+ * half spectrum as the image: a chunk is HSFFT_2D_CHUNK_MB / (copies x n0 x (n1/2+1) x 16) images,
+ * at least one; hsfft_r2c_2d and hsfft_r2c_2d_full hold one copy of a chunk, hsfft_c2r_2d two. */
+/* batch images of n0 x n1 reals -> batch half spectra of n0 x (n1/2+1) complex (row pitch n1/2+1):
+ * bins 0..n1/2 of the reference's fft_r2c_exec(r1) on every row (what hsfft_r2c_batched_compact
+ * writes), then the reference's fft_exec(p0) on each of the n1/2+1 columns of that result.  This
+ * order is part of the contract: results are bit-identical to the reference applied that way. */
+int hsfft_r2c_2d(fft_object p0, fft_real_object r1, const fft_type *d_in, fft_data *d_out, int batch);
+/* same transform, reference-style full layout: n0 x n1 complex per image.  Columns k1 <= n1/2 hold
+ * the words of hsfft_r2c_2d.  The mirror half, columns k1 = n1/2+1 .. n1-1, is a copy with a sign
+ * flip, not a second column transform: out[k0][k1] = (re, -im) of out[(n0-k0) % n0][n1-k1], where
+ * -im flips the sign bit (of zeros and NaNs too), as the reference builds the upper half of its
+ * own 1D r2c rows.  With n1 == 2 there is no mirror column.  Every element is written once. */
+int hsfft_r2c_2d_full(fft_object p0, fft_real_object r1, const fft_type *d_in, fft_data *d_out, int batch);
+/* batch half spectra n0 x (n1/2+1) -> batch images of n0 x n1 reals: fft_exec(p0) on each of the
+ * n1/2+1 columns of the input, then the reference's fft_c2r_exec(r1) on every row of that result
+ * (it reads bins 0..n1/2, here at pitch n1/2+1).  Compositional: holds for any input words,
+ * Hermitian-consistent or not. */
+int hsfft_c2r_2d(fft_object p0, fft_real_object r1, const fft_data *d_in, fft_type *d_out, int batch);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */
@@ -144,6 +170,10 @@ int hsfft_count_diff_words(const void *d_a, const void *d_b, size_t bytes, uint6
 /* Stream-copy reference: `iters` device copies of `bytes` (multiple of 16) from d_src to
  * d_dst, event-timed; the practical HBM ceiling reported next to the FFT numbers. */
 int hsfft_bench_copy(const void *d_src, void *d_dst, size_t bytes, int iters, float *ms);
+/* The last step of hsfft_r2c_2d_full alone, event-timed (`iters` launches after one warm-up, total
+ * milliseconds in *ms): batch transposed half spectra d_in[b][k1][k0] ((n1/2+1) x n0) to the full
+ * layout d_out[b][k0][k1] (n0 x n1), mirror half included.  n1 even, batch >= 1. */
+int hsfft_bench_transpose_herm(const fft_data *d_in, fft_data *d_out, int n0, int n1, int batch, int iters, float *ms);
 
 /* Bluestein M = 2^18 (e.g. N = 99991) runs as one persistent launch whose workgroups must all
  * be resident at once; the library checks that with the occupancy API before launching, and a

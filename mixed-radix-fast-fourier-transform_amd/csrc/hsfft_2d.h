@@ -7,6 +7,11 @@
  * The 1D transforms are hs_c2c_rows() unchanged -- every planned length over contiguous rows --
  * and a transpose is a pure copy, so a 2D result is, word for word, the reference's fft_exec
  * applied to every row and then to every column of that result.
+ *
+ * The real 2D transforms (hsfft_r2c_2d, hsfft_r2c_2d_full, hsfft_c2r_2d) are built
+ * the same way from hs_r2c_rows() / hs_c2r_rows(), hs_c2c_rows() over the n1/2+1 columns of the
+ * half spectrum and the transposes; the full layout's mirror half is written by the one kernel
+ * they add, k_transpose_herm.
  */
 #include "hsfft_gpu.h"
 #include "hsfft_host.h"
@@ -108,11 +113,98 @@ static int transpose(const void *in, void *out, long long rows, long long cols, 
     return rc ? HSFFT_ERR_DEVICE : 0;
 }
 
+/* The last transpose of hsfft_r2c_2d_full: the transposed half spectrum in[b][k1][k0] (w = n1/2 + 1
+ * rows of n0) goes to the full layout out[b][k0][k1] (n0 rows of n1), and every element with
+ * 1 <= k1 <= n1/2 - 1 is stored a second time, imaginary part negated, at the mirrored index
+ * out[b][(n0 - k0) % n0][n1 - k1].  Together the two stores write each of the n0 x n1 outputs
+ * exactly once: the primary covers the columns 0..n1/2, the mirror the columns n1/2+1..n1-1.
+ *
+ * Staging as in k_transpose: 256 threads, one TS x TS tile of the source, LDS pitch TS + 1, edge
+ * guards on both sides, 64-bit indices, the batch flattened into the 1D grid.  A wave-instruction
+ * of the primary store covers one run of consecutive k1 of one output row; its mirror store
+ * covers the same run of another row with the lane order reversed, so it coalesces the same way.
+ * The negation is a sign-bit flip (zeros and NaNs included); no other arithmetic on the data. */
+template <int TS>
+__global__ __launch_bounds__(256) void k_transpose_herm(const v2d *__restrict__ in, v2d *__restrict__ out, long long n0,
+                                                        long long n1, long long ntr, long long ntc, long long tile0)
+{
+    extern __shared__ v2d tr_tile[];
+    constexpr int P = TS + 1, RY = 256 / TS, NK = TS / RY;
+    const long long h = n1 / 2, w = h + 1;
+    const long long t = tile0 + blockIdx.x, per = ntr * ntc;
+    const long long b = t / per, rem = t - b * per;
+    const long long tr = rem / ntc, tc = rem - tr * ntc;
+    const int tx = threadIdx.x % TS, ty = threadIdx.x / TS;
+    const long long r0 = tr * TS, c0 = tc * TS; /* source row = k1, source column = k0 */
+    const v2d *src = in + b * w * n0;
+    v2d *dst = out + b * n0 * n1;
+    v2d v[NK];
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long r = r0 + ty + k * RY, c = c0 + tx;
+        if (r < w && c < n0) v[k] = src[r * n0 + c];
+    }
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long r = r0 + ty + k * RY, c = c0 + tx;
+        if (r < w && c < n0) tr_tile[(ty + k * RY) * P + tx] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long k0 = c0 + ty + k * RY, k1 = r0 + tx;
+        if (k0 < n0 && k1 < w) {
+            v2d e = tr_tile[tx * P + ty + k * RY];
+            dst[k0 * n1 + k1] = e;
+            if (k1 >= 1 && k1 < h) {
+                e.y = -e.y;
+                dst[(k0 ? n0 - k0 : 0) * n1 + (n1 - k1)] = e;
+            }
+        }
+    }
+}
+
+/* (device lock held by the caller) queue the mirrored transposes of `batch` images */
+static int launch_herm(const void *in, void *out, long long n0, long long n1, long long batch)
+{
+    typedef void (*kfn)(const v2d *, v2d *, long long, long long, long long, long long, long long);
+    const int ts = hs_env_int("HSFFT_TR_TILE", 64) == 32 ? 32 : 64; /* the knob of launch() */
+    const kfn fn = ts == 64 ? k_transpose_herm<64> : k_transpose_herm<32>;
+    const size_t lds = (size_t)ts * (ts + 1) * sizeof(v2d);
+    const long long ntr = (n1 / 2 + 1 + ts - 1) / ts, ntc = (n0 + ts - 1) / ts;
+    if (ntr > MAX_GRID / ntc) {
+        snprintf(g_err, sizeof g_err, "mirrored transpose: %lld x %lld tiles per image", ntr, ntc);
+        return -1;
+    }
+    if (lds > 65536) { /* once per device (callers hold the device lock) */
+        static bool lds_set[HS_MAX_DEV];
+        bool &done = lds_set[cur_dev()];
+        if (!done) HCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    const long long total = batch * ntr * ntc;
+    for (long long t0 = 0; t0 < total; t0 += MAX_GRID) {
+        const long long g = total - t0 < MAX_GRID ? total - t0 : MAX_GRID;
+        hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(256), lds, stream(), (const v2d *)in, (v2d *)out, n0, n1, ntr, ntc,
+                           t0);
+        HCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+static int transpose_herm(const void *in, void *out, long long n0, long long n1, long long batch)
+{
+    const int rc = launch_herm(in, out, n0, n1, batch);
+    if (rc) hs_seterr("mirrored transpose: %s", g_err);
+    return rc ? HSFFT_ERR_DEVICE : 0;
+}
+
 /* Scratch of the 2D paths (HS_SCR_2D): HSFFT_2D_CHUNK_MB (default 1024) bounds it.  A call walks
  * its batch in chunks of whole images: bytes / (copies * image bytes) images, at least one, at
  * most the batch and at most what keeps a chunk's row count an int; halved while the allocation
- * fails; the last chunk may be ragged.  hsfft_exec_2d needs one copy of the chunk, and
- * hsfft_exec_columns two. */
+ * fails; the last chunk may be ragged.  hsfft_exec_2d needs one copy of the chunk and
+ * hsfft_exec_columns two; for the real 2D transforms the image is the half spectrum, n0 x
+ * (n1/2+1) elements: hsfft_r2c_2d and hsfft_r2c_2d_full need one copy, hsfft_c2r_2d two. */
 static void *chunk_scratch(long long img_elems, int max_dim, int copies, int batch, long long *per_chunk)
 {
     const size_t img_bytes = sizeof(fft_data) * (size_t)img_elems;
@@ -194,11 +286,93 @@ static int exec_columns(hs_entry *e, const fft_data *in, fft_data *out, int ncol
     return 0;
 }
 
+/* the half spectrum of the real 2D transforms: n0 rows of w = n1/2 + 1 bins; 0 (message set) if
+ * it is too large */
+static long long half_image(const char *who, long long n0, long long w)
+{
+    if (n0 * w <= (1LL << 40)) return n0 * w;
+    hs_seterr("%s: half spectrum of %lld x %lld bins is too large", who, n0, w);
+    return 0;
+}
+
+/* (device lock held) r2c of r1 on the rows, then e0 on the w = n1/2 + 1 columns of `batch` real
+ * n0 x n1 images, per chunk with one scratch copy S of the chunk's half spectra: r2c-compact rows
+ * in -> S (n0 x w), transpose S -> T, rows T -> S (the columns, now contiguous: w x n0), and the
+ * last transpose S -> out.  full 0: out holds n0 x w per image, T is the output chunk itself and
+ * the last transpose is the plain one.  full 1: out holds n0 x n1 per image, T is the front of
+ * the (no smaller) output chunk and the last transpose also writes the mirror half. */
+static int r2c_2d(hs_entry *e0, fft_real_object r1, const fft_type *in, fft_data *out, int batch, int full)
+{
+    const long long n0 = e0->N, h = r1->cobj->N, n1 = 2 * h, w = h + 1;
+    const long long img = half_image(full ? "hsfft_r2c_2d_full" : "hsfft_r2c_2d", n0, w), oimg = full ? n0 * n1 : img;
+    if (!img) return HSFFT_ERR_ARG;
+    long long ci;
+    fft_data *S = (fft_data *)chunk_scratch(img, (int)(n0 > w ? n0 : w), 1, batch, &ci);
+    if (!S) return HSFFT_ERR_NOMEM;
+    for (long long b0 = 0; b0 < batch; b0 += ci) {
+        const long long cb = batch - b0 < ci ? batch - b0 : ci;
+        fft_data *ob = out + b0 * oimg;
+        int rc = hs_r2c_rows(r1, in + b0 * n0 * n1, S, (int)(cb * n0), 1);
+        if (!rc) rc = transpose(S, ob, n0, w, cb);
+        if (!rc) rc = rows(e0, ob, S, cb * w);
+        if (!rc) rc = full ? transpose_herm(S, ob, n0, n1, cb) : transpose(S, ob, w, n0, cb);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+/* (device lock held) e0 on the w columns of `batch` half spectra of n0 x w, then c2r of r1 on
+ * every row, per chunk with two scratch copies (the real output is smaller than a half spectrum,
+ * so it cannot hold an intermediate): transpose in -> S0, rows S0 -> S1, transpose S1 -> S0, c2r
+ * rows S0 (pitch w) -> out. */
+static int c2r_2d(hs_entry *e0, fft_real_object r1, const fft_data *in, fft_type *out, int batch)
+{
+    const long long n0 = e0->N, h = r1->cobj->N, n1 = 2 * h, w = h + 1;
+    const long long img = half_image("hsfft_c2r_2d", n0, w);
+    if (!img) return HSFFT_ERR_ARG;
+    long long ci;
+    fft_data *S0 = (fft_data *)chunk_scratch(img, (int)(n0 > w ? n0 : w), 2, batch, &ci);
+    if (!S0) return HSFFT_ERR_NOMEM;
+    fft_data *S1 = S0 + ci * img;
+    for (long long b0 = 0; b0 < batch; b0 += ci) {
+        const long long cb = batch - b0 < ci ? batch - b0 : ci;
+        int rc = transpose(in + b0 * img, S0, n0, w, cb);
+        if (!rc) rc = rows(e0, S0, S1, cb * w);
+        if (!rc) rc = transpose(S1, S0, w, n0, cb);
+        if (!rc) rc = hs_c2r_rows(r1, S0, NULL, w, out + b0 * n0 * n1, (int)(cb * n0));
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+/* the byte ranges [a, a + na) and [b, b + nb) share a byte */
+static bool overlap_bytes(const void *a, uintptr_t na, const void *b, uintptr_t nb)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb ? pb - pa < na : pa - pb < nb;
+}
+
 /* the byte ranges [a, a + n) and [b, b + n) share a byte */
 static bool overlap(const void *a, const void *b, long long elems)
 {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, n = (uintptr_t)elems * sizeof(fft_data);
-    return pa < pb ? pb - pa < n : pa - pb < n;
+    const uintptr_t n = (uintptr_t)elems * sizeof(fft_data);
+    return overlap_bytes(a, n, b, n);
+}
+
+/* argument check of the three real 2D entry points; the real side holds n0 x n1 doubles per
+ * image and the complex side `cplx_cols` bins per row.  0, or HSFFT_ERR_ARG with the message set */
+static int real_2d_args(const char *who, fft_object p0, fft_real_object r1, const void *d_real, const void *d_cplx,
+                        int full, int batch)
+{
+    bool bad = !p0 || !r1 || !r1->cobj || !d_real || !d_cplx || d_real == d_cplx || batch < 0 || p0->N < 1 ||
+               r1->cobj->N < 1;
+    if (!bad) {
+        const uintptr_t n0 = (uintptr_t)p0->N, h = (uintptr_t)r1->cobj->N, cols = full ? 2 * h : h + 1;
+        bad = overlap_bytes(d_real, sizeof(fft_type) * n0 * 2 * h * (uintptr_t)batch, d_cplx,
+                            sizeof(fft_data) * n0 * cols * (uintptr_t)batch);
+    }
+    if (bad) hs_seterr("%s: invalid arguments", who);
+    return bad ? HSFFT_ERR_ARG : 0;
 }
 
 }  // namespace tr2d
@@ -257,6 +431,60 @@ int hsfft_exec_columns(fft_object p, const fft_data *d_in, fft_data *d_out, int 
     hs_entry *e = hs_entry_get(p);
     rc = e ? tr2d::exec_columns(e, d_in, d_out, ncols, batch) : HSFFT_ERR_ARG;
     hs_entry_put(e);
+    hs_unlock_device(d);
+    return rc;
+}
+
+/* the three real 2D entry points: mode 0 hsfft_r2c_2d, 1 hsfft_r2c_2d_full, 2 hsfft_c2r_2d */
+static int real_2d(const char *who, int mode, fft_object p0, fft_real_object r1, const void *d_in, void *d_out,
+                   int batch)
+{
+    hs_seterr("%s", "");
+    int rc = tr2d::real_2d_args(who, p0, r1, mode == 2 ? d_out : d_in, mode == 2 ? d_in : d_out, mode == 1, batch);
+    if (rc || batch == 0) return rc;
+    rc = hs_require_gpu();
+    if (rc) return rc;
+    const int d = hs_lock_device();
+    hs_entry *e0 = hs_entry_get(p0);
+    rc = !e0         ? HSFFT_ERR_ARG
+         : mode == 2 ? tr2d::c2r_2d(e0, r1, (const fft_data *)d_in, (fft_type *)d_out, batch)
+                     : tr2d::r2c_2d(e0, r1, (const fft_type *)d_in, (fft_data *)d_out, batch, mode);
+    hs_entry_put(e0);
+    hs_unlock_device(d);
+    return rc;
+}
+
+int hsfft_r2c_2d(fft_object p0, fft_real_object r1, const fft_type *d_in, fft_data *d_out, int batch)
+{
+    return real_2d("hsfft_r2c_2d", 0, p0, r1, d_in, d_out, batch);
+}
+
+int hsfft_r2c_2d_full(fft_object p0, fft_real_object r1, const fft_type *d_in, fft_data *d_out, int batch)
+{
+    return real_2d("hsfft_r2c_2d_full", 1, p0, r1, d_in, d_out, batch);
+}
+
+int hsfft_c2r_2d(fft_object p0, fft_real_object r1, const fft_data *d_in, fft_type *d_out, int batch)
+{
+    return real_2d("hsfft_c2r_2d", 2, p0, r1, d_in, d_out, batch);
+}
+
+int hsfft_bench_transpose_herm(const fft_data *d_in, fft_data *d_out, int n0, int n1, int batch, int iters, float *ms)
+{
+    hs_seterr("%s", "");
+    if (!d_in || !d_out || !ms || iters < 1 || batch < 1 || n0 < 1 || n1 < 2 || n1 % 2 ||
+        tr2d::overlap_bytes(d_in, sizeof(fft_data) * (uintptr_t)n0 * (n1 / 2 + 1) * batch, d_out,
+                            sizeof(fft_data) * (uintptr_t)n0 * n1 * batch)) {
+        hs_seterr("hsfft_bench_transpose_herm: invalid arguments");
+        return HSFFT_ERR_ARG;
+    }
+    int rc = hs_require_gpu();
+    if (rc) return rc;
+    const int d = hs_lock_device();
+    rc = tr2d::transpose_herm(d_in, d_out, n0, n1, batch); /* warm-up, outside the timing */
+    if (!rc && hsd_timer_start()) rc = HSFFT_ERR_DEVICE;
+    for (int i = 0; i < iters && !rc; i++) rc = tr2d::transpose_herm(d_in, d_out, n0, n1, batch);
+    if (!rc && hsd_timer_stop(ms)) rc = HSFFT_ERR_DEVICE;
     hs_unlock_device(d);
     return rc;
 }

@@ -93,6 +93,9 @@ int hs_c2c_rows(hs_entry *e, const void *in, long long idist, void *out, long lo
  * not allow it (caller falls back to c2c + split), 0 on success, < 0 on error */
 int hs_r2c_fused(hs_entry *e, const void *in, long long idist, void *Z, void *X, long long xdist, const void *tw2,
                  int batch, int compact);
+/* r2c of `batch` contiguous rows (hsfft_real.c; device lock held): compact 0 writes the
+ * reference's mirrored rows of N bins, 1 rows of N/2+1 bins (bins 0..N/2, the same words) */
+int hs_r2c_rows(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch, int compact);
 /* c2r of rows xdist complex apart (hsfft_real.c); d_b != NULL: of the product d_a .* d_b */
 int hs_c2r_rows(fft_real_object r, const fft_data *d_a, const fft_data *d_b, long long xdist, fft_type *d_out,
                 int batch);
@@ -115,9 +118,10 @@ enum {
     HS_SCR_BLUE_MID2 = 8, /* Bluestein second intermediate (fused middle kernel) */
     HS_SCR_HOST_OUT = 9,  /* hsfft_exec_batched_host: two download slots */
     HS_SCR_CONV_SPEC = 10,/* convolution: both compact spectra */
-    HS_SCR_2D = 11,       /* hsfft_exec_2d / hsfft_exec_columns (hsfft_2d.h): the chunk between the row
-                           * transforms and the transposes; a class of its own, because the row
-                           * transforms in between use the chain and Bluestein classes */
+    HS_SCR_2D = 11,       /* hsfft_exec_2d / hsfft_exec_columns / the 2D real transforms (hsfft_2d.h): the
+                           * chunk between the row transforms and the transposes; a class of its own,
+                           * because the row transforms in between use the chain, Bluestein and
+                           * HS_SCR_REAL_Z classes */
     HS_NSCRATCH = 12
 };
 void *hs_scratch(int cls, size_t bytes);

@@ -137,7 +137,7 @@ static fft_data *real_chunk(int h, int batch, long long *chunk)
  * 1: bins 0..N/2 per row (rows of N/2+1 complex), the non-redundant half
  * -- 16 B written per real sample instead of 24 for the same values (bit-identical to bins
  * 0..N/2 of the mirrored rows) */
-static int r2c_rows(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch, int compact)
+int hs_r2c_rows(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch, int compact)
 {
     hs_entry *e = hs_entry_get(r->cobj);
     void *tw2 = e ? tw2_device(r) : NULL;
@@ -203,7 +203,7 @@ int hsfft_r2c_batched(fft_real_object r, const fft_type *d_in, fft_data *d_out, 
 {
     int d, rc = real_enter("hsfft_r2c_batched", r, d_in, d_out, batch, &d);
     if (rc) return rc < 0 ? rc : 0;
-    rc = r2c_rows(r, d_in, d_out, batch, 0);
+    rc = hs_r2c_rows(r, d_in, d_out, batch, 0);
     hs_unlock_device(d);
     return rc;
 }
@@ -212,7 +212,7 @@ int hsfft_r2c_batched_compact(fft_real_object r, const fft_type *d_in, fft_data 
 {
     int d, rc = real_enter("hsfft_r2c_batched_compact", r, d_in, d_out, batch, &d);
     if (rc) return rc < 0 ? rc : 0;
-    rc = r2c_rows(r, d_in, d_out, batch, 1);
+    rc = hs_r2c_rows(r, d_in, d_out, batch, 1);
     hs_unlock_device(d);
     return rc;
 }

@@ -63,6 +63,9 @@ SIGNATURES = {
     "hsfft_transpose_batched": (CI, [VP, VP, CI, CI, CI]),
     "hsfft_exec_2d": (CI, [VP, VP, VP, VP, CI]),
     "hsfft_exec_columns": (CI, [VP, VP, VP, CI, CI]),
+    "hsfft_r2c_2d": (CI, [VP, VP, VP, VP, CI]),
+    "hsfft_r2c_2d_full": (CI, [VP, VP, VP, VP, CI]),
+    "hsfft_c2r_2d": (CI, [VP, VP, VP, VP, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -71,6 +74,7 @@ SIGNATURES = {
     "hsfft_time_exec_host": (CI, [VP, VP, VP, CI, CI, CI, ctypes.POINTER(ctypes.c_double)]),
     "hsfft_exec_multi": (CI, [VP, VP, VP, CI, CI]),
     "hsfft_bench_copy": (CI, [VP, VP, ctypes.c_size_t, CI, ctypes.POINTER(ctypes.c_float)]),
+    "hsfft_bench_transpose_herm": (CI, [VP, VP, CI, CI, CI, CI, ctypes.POINTER(ctypes.c_float)]),
     "hsfft_bluestein_fallbacks": (ctypes.c_longlong, []),
     "hsfft_thread_streams_created": (ctypes.c_longlong, []),
     "hsfft_count_diff_words": (CI, [VP, VP, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]),
@@ -292,6 +296,75 @@ def fft2(x, sgn=1):
             release()
 
 
+def r2c_2d(plan0, rplan1, d_in, d_out, batch):
+    """batch real images of plan0.n x rplan1.n -> half spectra of plan0.n x (rplan1.n/2+1): r2c of
+    rplan1 on the rows, then plan0 on the columns"""
+    return check(lib().hsfft_r2c_2d(plan0.ptr, rplan1.ptr, VP(d_in.ptr), VP(d_out.ptr), batch), "r2c_2d")
+
+
+def r2c_2d_full(plan0, rplan1, d_in, d_out, batch):
+    """the same transform in the full layout, plan0.n x rplan1.n complex per image (mirror half included)"""
+    return check(lib().hsfft_r2c_2d_full(plan0.ptr, rplan1.ptr, VP(d_in.ptr), VP(d_out.ptr), batch), "r2c_2d_full")
+
+
+def c2r_2d(plan0, rplan1, d_in, d_out, batch):
+    """batch half spectra of plan0.n x (rplan1.n/2+1) -> real images of plan0.n x rplan1.n: plan0 on
+    the columns, then c2r of rplan1 on the rows"""
+    return check(lib().hsfft_c2r_2d(plan0.ptr, rplan1.ptr, VP(d_in.ptr), VP(d_out.ptr), batch), "c2r_2d")
+
+
+def _real_2d(call, x, n0, n1, sgn, out_dtype, out_shape):
+    """plan (n0, n1, sgn), upload x, run call(p0, r1, d_in, d_out, batch), download"""
+    batch = x.size // (x.shape[-2] * x.shape[-1])
+    out_bytes = int(np.prod(out_shape)) * np.dtype(out_dtype).itemsize
+    made = []
+    try:
+        p0 = Plan(n0, sgn)
+        made.append(p0.close)
+        r1 = RealPlan(n1, sgn)
+        made.append(r1.close)
+        d_in = DeviceBuffer.from_array(x)
+        made.append(d_in.free)
+        d_out = DeviceBuffer(out_bytes)
+        made.append(d_out.free)
+        call(p0, r1, d_in, d_out, batch)
+        synchronize()
+        return d_out.to_array(out_dtype).reshape(out_shape)
+    finally:
+        for release in reversed(made):
+            release()
+
+
+def rfft2(x, sgn=1, full=False):
+    """2D r2c over the last two axes of a float64 array of shape (..., n0, n1), n1 even, unscaled:
+    the half spectrum (..., n0, n1/2+1), or with full=True the full layout (..., n0, n1); plans,
+    uploads, runs hsfft_r2c_2d / hsfft_r2c_2d_full and downloads"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim < 2:
+        raise ValueError("rfft2 needs an array of at least two dimensions")
+    n0, n1 = x.shape[-2:]
+    if n1 % 2:
+        raise ValueError("rfft2 needs an even last axis")
+    shape = x.shape[:-1] + (n1 if full else n1 // 2 + 1,)
+    if x.size == 0:
+        return np.empty(shape, dtype=np.complex128)
+    return _real_2d(r2c_2d_full if full else r2c_2d, x, n0, n1, sgn, np.complex128, shape)
+
+
+def irfft2(X, n1, sgn=-1):
+    """2D c2r over the last two axes of a complex128 array of half spectra (..., n0, n1/2+1),
+    unscaled: real images (..., n0, n1); plans, uploads, runs hsfft_c2r_2d and downloads"""
+    X = np.ascontiguousarray(X, dtype=np.complex128)
+    if X.ndim < 2:
+        raise ValueError("irfft2 needs an array of at least two dimensions")
+    if n1 < 2 or n1 % 2 or X.shape[-1] != n1 // 2 + 1:
+        raise ValueError("irfft2 needs an even n1 and a last axis of n1/2+1 bins")
+    shape = X.shape[:-1] + (n1,)
+    if X.size == 0:
+        return np.empty(shape, dtype=np.float64)
+    return _real_2d(c2r_2d, X, X.shape[-2], n1, sgn, np.float64, shape)
+
+
 def r2c_batched(rplan, d_in, d_out, batch):
     return check(lib().hsfft_r2c_batched(rplan.ptr, VP(d_in.ptr), VP(d_out.ptr), batch), "r2c_batched")
 
@@ -337,6 +410,14 @@ def time_batched(plan, d_in, d_out, batch, iters, max_pass=16):
 def bench_copy(d_src, d_dst, nbytes, iters):
     ms = ctypes.c_float(0.0)
     check(lib().hsfft_bench_copy(VP(d_src.ptr), VP(d_dst.ptr), nbytes, iters, ctypes.byref(ms)), "bench_copy")
+    return ms.value
+
+
+def bench_transpose_herm(d_in, d_out, n0, n1, batch, iters):
+    """milliseconds of `iters` mirrored transposes (the last step of r2c_2d_full), event-timed"""
+    ms = ctypes.c_float(0.0)
+    check(lib().hsfft_bench_transpose_herm(VP(d_in.ptr), VP(d_out.ptr), n0, n1, batch, iters, ctypes.byref(ms)),
+          "bench_transpose_herm")
     return ms.value
 
 
