@@ -6,7 +6,7 @@
  *
  * Why (measured, round 2, c4 = 99991 x 8192): the three row-looped kernels take 1.24 / 2.11 /
  * 1.52 ms per 1024 rows with the intermediates in HBM, 0.91 / 1.29 / 1.17 ms with every row
- * aliased to one on-die image (HSFFT_DEV_ALIAS=2, timing only) -- 21 vs 31 GSamples/s.  A
+ * aliased to one on-die image (a timing-only probe, removed since) -- 21 vs 31 GSamples/s.  A
  * group holds ONE row in flight (two 4 MiB images), so the eight groups' intermediates (64 MiB)
  * stay in the 256 MiB Infinity Cache instead of crossing HBM twice per row.
  *

@@ -518,52 +518,10 @@ static int launch_pass(hs_entry *e, hs_devstate *ds, int i, const hsd_launch *d)
     l.tw = ds->d_tw;
     l.tw_t = ds->tw_t;
     l.gcs = (const double *)ds->d_gcs;
-#ifdef HSFFT_DEV_PROBES
-    /* development build only: every row aliased to one buffer (on-die timing, results wrong) */
-    if (hs_env_int("HSFFT_DEV_ALIAS", 0) & 1) l.idist = l.odist = 0;
-#endif
     int rc = hsd_run_pass(&e->pass[i], &l);
     if (rc) hs_seterr("pass %d: %s", i, hsd_errstr());
     return rc;
 }
-
-#ifdef HSFFT_DEV_PROBES
-/* Development build only (round 6: measured slower, 52-67 vs 91 GSamples/s on c2 -- DESIGN.md
- * §5).  Two-pass chain over the batch in chunks of `chunk` rows, software-pipelined over two
- * streams: pass A of chunk k+1 (library stream) overlaps pass B of chunk k (second stream),
- * ordered by events; at most `lag` chunks run ahead so the in-flight intermediates stay in
- * the 256 MiB Infinity Cache.  The library stream waits for the last pass B at the end. */
-static int run_pipelined(hs_entry *e, hs_devstate *ds, const hsd_launch *d, int chunk)
-{
-    const int lag = hs_env_int("HSFFT_PIPE_LAG", 2);
-    int rc = 0, k = 0;
-    for (long long c0 = 0; c0 < d->batch && !rc; c0 += chunk, k++) {
-        hsd_launch a = *d, b = *d; /* pass A: the load hook; pass B, in place: the store hook */
-        a.in = (const fft_data *)d->in + c0 * d->idist;
-        a.out = b.out = (fft_data *)d->out + c0 * d->odist;
-        a.batch = b.batch = (int)(d->batch - c0 < chunk ? d->batch - c0 : chunk);
-        a.store_op = HS_STORE_PLAIN;
-        a.store_aux = NULL;
-        if (k) a.done = NULL;
-        b.in = b.out;
-        b.idist = d->odist;
-        b.load_op = HS_LOAD_PLAIN;
-        b.load_aux = NULL;
-        b.done = NULL;
-        hsd_select_stream(0);
-        if (k >= lag) rc = hsd_event_wait(2 * (k - lag) + 1); /* pass B of chunk k-lag done */
-        if (!rc) rc = launch_pass(e, ds, 0, &a);
-        if (!rc) rc = hsd_event_record(2 * k);
-        hsd_select_stream(1);
-        if (!rc) rc = hsd_event_wait(2 * k);
-        if (!rc) rc = launch_pass(e, ds, 1, &b);
-        if (!rc) rc = hsd_event_record(2 * k + 1);
-    }
-    hsd_select_stream(0);
-    if (!rc && k > 0) rc = hsd_event_wait(2 * (k - 1) + 1);
-    return rc;
-}
-#endif
 
 /* One mixed-radix transform of length M per row of *d, chained over the plan's passes.  Reads
  * d->in (never written), writes d->out.  Intermediate buffers come from the scratch pool; the
@@ -592,13 +550,6 @@ static int run_chain(hs_entry *e, hs_devstate *ds, const hsd_launch *d)
         if (per < 1) per = 1;
         if (chunk > per) chunk = per;
     }
-#ifdef HSFFT_DEV_PROBES
-    else { /* development build only: all passes over a few rows at a time, the intermediate in
-            * the 256 MiB Infinity Cache between passes (HSFFT_MALL_ROWS; measured slower) */
-        const int rows = hs_env_int("HSFFT_MALL_ROWS", 0);
-        if (rows > 0 && chunk > rows) chunk = rows;
-    }
-#endif
     void *S[2] = {NULL, NULL};
     for (int k = 0; k < need; k++) {
         S[k] = hs_scratch(k ? HS_SCR_CHAIN1 : HS_SCR_CHAIN0, sizeof(fft_data) * (size_t)(chunk * M));
@@ -607,12 +558,6 @@ static int run_chain(hs_entry *e, hs_devstate *ds, const hsd_launch *d)
             return HSFFT_ERR_NOMEM;
         }
     }
-#ifdef HSFFT_DEV_PROBES
-    if (!need && n == 2 && chunk < batch && hs_env_int("HSFFT_PIPE", 0)) return run_pipelined(e, ds, d, (int)chunk);
-    const int dev_np = hs_env_int("HSFFT_DEV_NPASS", 0); /* development build only: stop after this many passes */
-#else
-    const int dev_np = 0;
-#endif
     hsd_launch l = *d;
     for (long long c0 = 0; c0 < batch; c0 += chunk) {
         l.batch = (int)(batch - c0 < chunk ? batch - c0 : chunk);
@@ -620,7 +565,7 @@ static int run_chain(hs_entry *e, hs_devstate *ds, const hsd_launch *d)
         l.idist = d->idist;
         l.load_op = d->load_op;
         int j = 0;
-        for (int i = 0; i < (dev_np > 0 && dev_np < n ? dev_np : n); i++) {
+        for (int i = 0; i < n; i++) {
             if (i == n - 1 || (i == n - 2 && last_inplace)) {
                 l.out = (fft_data *)d->out + c0 * d->odist;
                 l.odist = d->odist;
@@ -787,13 +732,6 @@ static int run_bluestein(hs_entry *e, hs_devstate *ds, const void *in, long long
         hs_seterr("bluestein scratch allocation of %lld bytes failed", (long long)(chunk * M * 16));
         return HSFFT_ERR_NOMEM;
     }
-#ifdef HSFFT_DEV_PROBES
-    /* development build only (results WRONG): every row of a chunk uses the same M-point
-     * intermediate, so the hand-offs between the three kernels stay on die */
-    const long long md = (hs_env_int("HSFFT_DEV_ALIAS", 0) & 2) ? 0 : M;
-#else
-    const long long md = M;
-#endif
     for (long long c0 = 0; c0 < batch; c0 += chunk) {
         const int cb = (int)(batch - c0 < chunk ? batch - c0 : chunk);
         const fft_data *ci = (const fft_data *)in + c0 * idist;
@@ -817,15 +755,15 @@ static int run_bluestein(hs_entry *e, hs_devstate *ds, const void *in, long long
             if (rc) return rc;
             continue;
         }
-        rc = hsd_blue_first(ci, idist, mid, md, ds->d_tw, ds->d_chirp, N, cb, e->sgn);
+        rc = hsd_blue_first(ci, idist, mid, M, ds->d_tw, ds->d_chirp, N, cb, e->sgn);
         if (rc < 0) hs_seterr("bluestein first pass: %s", hsd_errstr());
         if (rc == 1) rc = launch_pass(e, ds, 0, &fwd);
-        if (!rc && hsd_blue_mid(mid, mid2, md, ds->d_tw, ds->d_hk, cb, e->sgn, 0, e->sgn, -1 * e->sgn, 1)) {
+        if (!rc && hsd_blue_mid(mid, mid2, M, ds->d_tw, ds->d_hk, cb, e->sgn, 0, e->sgn, -1 * e->sgn, 1)) {
             hs_seterr("bluestein middle: %s", hsd_errstr());
             rc = HSFFT_ERR_DEVICE;
         }
         if (!rc) {
-            rc = hsd_blue_last(mid2, md, co, odist, ds->d_tw, ds->d_chirp, N, cb, e->sgn);
+            rc = hsd_blue_last(mid2, M, co, odist, ds->d_tw, ds->d_chirp, N, cb, e->sgn);
             if (rc < 0) hs_seterr("bluestein last pass: %s", hsd_errstr());
             if (rc == 1) rc = launch_pass(e, ds, 1, &inv);
         }
@@ -843,40 +781,6 @@ int hs_r2c_fused(hs_entry *e, const void *in, long long idist, void *Z, void *X,
         return 1; /* HSFFT_R2C_FUSE=0: pass B + k_r2c_post2 (r2c 2^22: 85 vs 93 GSamples/s fused) */
     hs_devstate *ds = devstate(e);
     if (!ds) return HSFFT_ERR_DEVICE;
-    /* HSFFT_R2C_OVL = S (measurement, development build; 27.97 / 24.75 / 23.87 vs 22.32 ms per
-     * 512 rows for S = 32 / 64 / 128): the call in sub-chunks of S rows, pass A of every
-     * sub-chunk on the library stream and the split walk of sub-chunk s on the pipeline stream
-     * behind pass A(s) only, so the walks (latency-bound) overlap the later pass As
-     * (bandwidth-bound); Z holds every row, so nothing is reused; the library stream then waits
-     * for the last walk */
-#ifdef HSFFT_DEV_PROBES
-    const int ovl = hs_env_int("HSFFT_R2C_OVL", 0); /* development build only: measured slower */
-    if (ovl > 0 && batch > ovl && hsd_stream_index() == 0) {
-        const int ns = (batch + ovl - 1) / ovl;
-        int rc = 0;
-        for (int s = 0; s < ns && !rc; s++) {
-            const long long r0 = (long long)s * ovl;
-            const int nb = (int)(batch - r0 < ovl ? batch - r0 : ovl);
-            void *Zs = (char *)Z + r0 * e->M * (long long)sizeof(fft_data);
-            hsd_select_stream(0);
-            const hsd_launch ls = c2c_launch(e, (const char *)in + r0 * idist * (long long)sizeof(fft_data), idist, Zs,
-                                             e->M, nb);
-            rc = launch_pass(e, ds, 0, &ls);
-            if (!rc) rc = hsd_event_record(2 * s) ? HSFFT_ERR_DEVICE : 0;
-            hsd_select_stream(1);
-            if (!rc) rc = hsd_event_wait(2 * s) ? HSFFT_ERR_DEVICE : 0;
-            if (!rc && hsd_r2c_last(Zs, e->M, (char *)X + r0 * xdist * (long long)sizeof(fft_data), xdist, ds->d_tw,
-                                    tw2, e->M, p1->B, nb, e->sgn, compact)) {
-                hs_seterr("r2c last pass: %s", hsd_errstr());
-                rc = HSFFT_ERR_DEVICE;
-            }
-            if (!rc) rc = hsd_event_record(2 * s + 1) ? HSFFT_ERR_DEVICE : 0;
-        }
-        hsd_select_stream(0);
-        if (!rc) rc = hsd_event_wait(2 * (ns - 1) + 1) ? HSFFT_ERR_DEVICE : 0;
-        return rc;
-    }
-#endif
     const hsd_launch l = c2c_launch(e, in, idist, Z, e->M, batch);
     int rc = launch_pass(e, ds, 0, &l);
     if (!rc && hsd_r2c_last(Z, e->M, X, xdist, ds->d_tw, tw2, e->M, p1->B, batch, e->sgn, compact)) {

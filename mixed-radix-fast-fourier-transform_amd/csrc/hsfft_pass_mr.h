@@ -605,43 +605,10 @@ __device__ __forceinline__ void xchg1_ab_g45(double *x, double *ld, int jt)
         for (int i = 0; i < 7; i++) x[c * 7 + i] = ld[(4 * h + c + 8 * i) * G45 + g];
 }
 
-/* TWN 3: the stage-5 twiddles of steps d >= 1 (k-blocks jj = 1, 2, 3 of thread A and 5, 6 of
- * thread B, 225 k x 7 each) are copied into LDS before the first store of the row -- four blocks
- * into the free exchange image, the fifth behind the stage twiddle copy -- transposed to
- * [i-1][k - 225 jj]; step 0 reads its run from global as before (no store precedes it).  So no
- * twiddle load waits behind a store burst (vmcnt is in order). */
-constexpr int F45_BLK = 1575; /* 225 k x 7 entries */
-__device__ __forceinline__ const double2 *f45_slot(const double2 *img, const double2 *extra, int s)
-{
-    return s < 4 ? img + s * F45_BLK : extra;
-}
-template <int P, int TPG>
-__device__ __forceinline__ void f45_tw_copy(const double2 *tw, double2 *img, double2 *extra, int jt)
-{
-    constexpr int G45 = P / 56, L5 = 7 * G45, NE = 5 * F45_BLK, NIT = (NE + TPG - 1) / TPG;
-    static_assert(G45 * 7 == F45_BLK, "F45 block");
-    double2 v[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        int e = it * TPG + jt;
-        if (e >= NE) e = NE - 1;
-        const int blk = e / F45_BLK, r = e % F45_BLK, jj = blk < 3 ? blk + 1 : blk + 2;
-        v[it] = pf::ldg(tw, (unsigned)(L5 - 1 + 7 * G45 * jj + r) * 16u);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        const int e = it * TPG + jt;
-        if (e >= NE) continue;
-        const int blk = e / F45_BLK, r = e % F45_BLK;
-        const_cast<double2 *>(f45_slot(img, extra, blk))[(r % 7) * G45 + r / 7] = v[it];
-    }
-}
-
 /* stages 4 (radix 7) and 5 (radix 8) of the pair's group, then the row's stores */
 template <int P, int TPG, bool CONJ, int TWN = 0>
 __device__ __forceinline__ void fused45_pair(double *xr, double *xi, const double2 *ltw, const double2 *tw,
-                                             double2 *out, int jt, int sgn, const double2 *timg = nullptr,
-                                             const double2 *textra = nullptr)
+                                             double2 *out, int jt, int sgn)
 {
     constexpr int G45 = P / 56, L4 = G45, L5 = 7 * G45;
     const int h = jt & 1, g0 = jt >> 1;
@@ -682,14 +649,8 @@ __device__ __forceinline__ void fused45_pair(double *xr, double *xi, const doubl
         const unsigned k = g + (unsigned)(h && d == 3 ? 0 : jj) * G45; /* B's d = 3 is idle: a valid k */
 #pragma unroll
         for (int i = 1; i < 8; i++) {
-            /* TWN 2 (timing probe, development builds): constant twiddles, results wrong */
             double2 t;
-            if constexpr (TWN == 2) t = make_double2(0.5, 0.25 * i);
-            else if constexpr (TWN == 3) {
-                /* slots 0-2: A's d = 1..3; 3, 4: B's d = 1, 2 (B's idle d = 3 reads slot 2) */
-                const int sl = h ? (d == 3 ? 2 : d + 2) : d - 1;
-                t = d == 0 ? pf::ldg(twb, (7 * k + i - 1) * 16u) : f45_slot(timg, textra, sl)[(i - 1) * G45 + g];
-            } else if constexpr (TWN == 4) {
+            if constexpr (TWN == 4) {
                 /* the plan's transposed copy of this stage's block at tw + P ([i-1][k]) */
                 t = pf::ldg(tw + P, ((i - 1) * L5 + k) * 16u);
             } else t = pf::ldg(twb, (7 * k + i - 1) * 16u);
@@ -886,13 +847,7 @@ __global__ __launch_bounds__(TPG) void k_row2(MArgs a)
             xchg1_ab_g45<R2, R3, LS::Lloc(2), P, TPG>(xr, img, jt);
             xchg1_ab_g45<R2, R3, LS::Lloc(2), P, TPG>(xi, img, jt);
             mark(a, tp, 3);
-            if constexpr (TWN == 3) {
-                __syncthreads(); /* every wave has read the image */
-                f45_tw_copy<P, TPG>(a.tw, reinterpret_cast<double2 *>(img), ltw + NT, jt);
-                __syncthreads();
-            }
-            fused45_pair<P, TPG, CONJ, TWN>(xr, xi, ltw, a.tw, out, jt, sgn, reinterpret_cast<const double2 *>(img),
-                                            ltw + NT);
+            fused45_pair<P, TPG, CONJ, TWN>(xr, xi, ltw, a.tw, out, jt, sgn);
             mark(a, tp, 6);
             if (a.dbg && threadIdx.x == 0) a.dbg[blockIdx.x * 8 + 7] += 1;
             continue;
@@ -1034,7 +989,7 @@ inline int launch(const hsd_pass *p, const hsd_launch *l, hipStream_t st)
     }
     if (v->row) { /* 12600 = [3,3,5,5,7,8]: k_row2 (the only whole-row variant) */
         constexpr int P = 12600, NT = 1574;
-        const size_t lds0 = (size_t)P * sizeof(double) + (size_t)NT * sizeof(double2);
+        const size_t lds = (size_t)P * sizeof(double) + (size_t)NT * sizeof(double2);
         if (l->batch <= 0) {
             snprintf(g_err, sizeof g_err, "mr: bad row batch=%d", l->batch);
             return -1;
@@ -1073,26 +1028,10 @@ inline int launch(const hsd_pass *p, const hsd_launch *l, hipStream_t st)
                                 : k_row2<3, 3, 5, 5, 7, 8, 512, false, true, false, 1, true, true, 0>);
         /* the next row's first group loaded before this row's first exchange instead of after
          * it: 6.11 vs 5.98 ms (round 4, removed) */
-        size_t lds = lds0;
-#ifdef HSFFT_DEV_PROBES
-        /* round 5, measured and removed: the stage-5 twiddles of steps 1-2 / 1-3 copied by LDS-DMA
-         * into the free exchange image before the row's stores, 5.83 / 6.17 vs 5.68 ms
-         * (profiles/r05e_c3_twn_c4_ul_ab.txt); the F45 exchange image with a padded pitch (no bank
-         * conflicts, no ds_read2_b64), 5.741 vs 5.749 ms (profiles/r05b_c3_xp_ab_and_cu_mask.txt) */
-        /* development build only (measurement): HSFFT_ROW_TWN=2 constant stage-5 twiddles, results
-         * wrong (5.46-5.49 ms: what the twiddle loads cost); 3 those of steps 1-3 copied into LDS
-         * before the row's stores (6.20 vs 5.89 ms).  Loading step d+1's run before step d's
-         * stores in registers spills 17 dwords: 7.01 vs 5.93 ms (removed) */
-        if (f45 && etwn && atoi(etwn) == 2 && !a.conj) fn = k_row2<3, 3, 5, 5, 7, 8, 512, false, true, false, 1, true, true, 2>;
-        if (f45 && etwn && atoi(etwn) == 3) {
-            fn = a.conj ? k_row2<3, 3, 5, 5, 7, 8, 512, true, true, false, 1, true, true, 3>
-                        : k_row2<3, 3, 5, 5, 7, 8, 512, false, true, false, 1, true, true, 3>;
-            lds = lds0 + (size_t)F45_BLK * sizeof(double2);
-        }
-#endif
         /* measured slower and removed (round 4): non-temporal row stores 6.32 vs 5.96 ms; the
          * next row's remaining groups copied into LDS by LDS-DMA before this row's stores, 6.15
-         * vs 5.94 (the load wait moves into the store phase: profiles/r04n_c3_dma_*) */
+         * vs 5.94 (the load wait moves into the store phase: profiles/r04n_c3_dma_*).  Round 5's
+         * stage-5 twiddle experiments (LDS copies, constant twiddles): DESIGN.md §5 */
         const int threads = 512;
         int ncu = 0, dev = 0;
         HCHK(hipGetDevice(&dev));

@@ -20,15 +20,6 @@
 
 namespace pf {
 
-#ifdef HSFFT_DEV_PROBES
-/* development build only (results WRONG when changed): mask on the k_local of the global
- * L = 512 twiddles of a 4096-point first pass (HSFFT_PFA_PROBE=1: 7, i.e. one 7-entry run) */
-__device__ unsigned pf_probe_twmask = 0xffffffffu;
-#define PF_TWMASK pf_probe_twmask
-#else
-#define PF_TWMASK 0xffffffffu
-#endif
-
 using r8::Args;
 using r8::Shape;
 
@@ -145,7 +136,7 @@ __device__ __forceinline__ void first_body(double (&xr)[8], double (&xi)[8], dou
         stage<8, SGN>(xr, xi, w, false);
     }
     if constexpr (N8 >= 3) {
-        if constexpr (TWG) tw8<CONJ>(w, gtw, S::Lloc(3), jt & (S::Lloc(3) - 1) & PF_TWMASK);
+        if constexpr (TWG) tw8<CONJ>(w, gtw, S::Lloc(3), jt & (S::Lloc(3) - 1));
         r8::exchange<8, S::Lloc(2), 8, TPG, P, G, true>(xr, xi, lds, jt, g);
         if constexpr (!TWG) tw8_lds<CONJ>(w, ltw, S::Lloc(3), jt & (S::Lloc(3) - 1));
         stage<8, SGN>(xr, xi, w, false);
@@ -461,229 +452,19 @@ __device__ __forceinline__ double2 grp_shift(double2 v)
     return make_double2(__shfl(v.x, src, 64), __shfl(v.y, src, 64));
 }
 
-/* ------------------------------------------------------------------ r2c split, 512-thread walk
- * k_r2c_walk's whole-line stores with k_r2c_fused's sequential hi / lo tiles, in ONE 8-wave
- * workgroup per CU with 256 VGPRs, software pipelined instead of relying on a second resident
- * workgroup: the lo tile's points and twiddle runs load while the hi tile is transformed, the
- * next hi tile's while the lo tile is transformed (two register buffers A / B, transformed in
- * place).  The lo thread writes all four streams of its pair; X[k] and X[h+k] go out on whole
- * lines through the one-lane shift and the carried entry (LDS, same thread), as in k_r2c_walk. */
-struct R2cBuf {
-    double r[8], i[8];
-    double2 w[7]; /* stage-2 twiddle run, coalesced order (redistributed when used) */
-    double2 l;    /* this thread's entry of the stage-0/1 twiddle runs (threads < 504) */
-};
-
-/* TWP (timing probe, -DHSFFT_DEV_PROBES builds only): every tile reads column 0's twiddle
- * runs (cache-resident; results wrong) */
-template <bool TWP = false>
-__device__ __forceinline__ void r2cw2_issue(R2cBuf &d, const double2 *row, unsigned B, unsigned q0, const double2 *tw,
-                                            unsigned tid)
-{
-    constexpr int TPG = 64;
-    const unsigned lane0 = ((tid >> 3) * B + q0 + (tid & 7)) * 16u;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const double2 v = ldg(row + (size_t)i * TPG * B, lane0);
-        d.r[i] = v.x;
-        d.i[i] = v.y;
-    }
-    const unsigned qt = TWP ? 0u : q0;
-    r8::Args ta;
-    ta.tw = tw;
-    ta.B = B;
-    r8::load_tw_co<64>(d.w, ta, (int)(tid >> 3), qt);
-    const unsigned t = tid < 504 ? tid : 0, r = t / 56, e = t % 56;
-    const long long src = r == 0 ? (long long)B - 1 + 7LL * qt + e : 8LL * B - 1 + 7LL * (qt + (long long)B * (r - 1)) + e;
-    d.l = tw[src];
-}
-
-/* twiddles of the buffered tile -> ltw (runs) and w2 (redistributed through the image) */
-__device__ __forceinline__ void r2cw2_tw(const R2cBuf &d, double2 (&w2)[7], double2 *lds, double2 *ltw, unsigned tid)
-{
-#pragma unroll
-    for (int i = 0; i < 7; i++) w2[i] = d.w[i];
-    __syncthreads(); /* earlier readers of the image and of ltw are done */
-    if (tid < 504) ltw[tid] = d.l;
-    r8::redistribute_tw(w2, lds);
-    __syncthreads();
-}
-
-constexpr int R2CW2_LDS = (512 * 8 + 504 + 1024) * 16;
-
-/* V (measurement variants; 0 is the default): bit 0 phase trace into a.dbg; -DHSFFT_DEV_PROBES
- * builds only (results WRONG): bit 1 twiddle2 read from one cache-resident line per lane group,
- * bit 2 every tile's stage-2 twiddles from column 0.  Measured and dropped (round 3):
- * non-temporal data loads and / or output stores (c5 88.3 / 91.3 / 85.2 vs 95.1-96.2 on one
- * box); the lo tile's twiddle2 prefetched by LDS-DMA and the hi tile's into registers during
- * the lo stages (bit-exact, 228 VGPRs: 104.6-105.0 vs 105.3-105.7 -- the wait moves from the
- * pairs phase to the lo phase); one output stream (X[N-k]) parked in LDS and stored during the
- * next tile's hi phase (bit-exact, 209 VGPRs, 152 KiB LDS: 103.0-103.2 vs 102.4-103.6 -- the
- * pairs phase sheds 0.7 us, the hi phase gains 2.1).  Probes: with no twiddle traffic at all c5
- * gains 2.5 % (108.3 / 107.7 vs 105.7 / 105.3): the twiddle re-reads are not what bounds the walk. */
-template <int SGN, int V = 0>
-__global__ __launch_bounds__(512, 2) void k_r2c_walk2(Args a, unsigned h, unsigned T, unsigned W)
-{
-    constexpr bool TRC = (V & 1) != 0, P_TW2 = (V & 2) != 0, P_TWS = (V & 4) != 0;
-    constexpr int P = 512, TPG = 64, G = 8;
-    extern __shared__ __attribute__((aligned(16))) double2 lds[];
-    double2 *ltw = lds + P * G, *cry = ltw + 504;
-    double *ld = reinterpret_cast<double *>(lds); /* [0, 4096): split image / hi imag, [4096, 8192): hi real */
-    /* a.tile_major (1, 2): consecutive blocks (one XCD) take the same walk segment of
-     * consecutive rows, so the segment's twiddle runs and twiddle2 slice are read from that
-     * XCD's L2 */
-    const unsigned blk = xcd_remap(blockIdx.x), nb = (unsigned)a.batch;
-    const unsigned b = a.tile_major ? blk % nb : blk / (W + 1), s = a.tile_major ? blk / nb : blk % (W + 1);
-    const unsigned tid0 = threadIdx.x, B = (unsigned)a.B, N = 2 * h;
-    const double2 *row = a.in + (long long)b * a.idist;
-    double2 *X = a.out + (long long)b * a.odist;
-    const double2 *w2t = a.saux;
-    if (s == W) { /* column 0 (k = u*B pairs with (P-u)*B), as k_r2c_fused */
-        const unsigned g = tid0 & 7, jt = tid0 >> 3;
-        double xr[8], xi[8];
-        double2 w2[7];
-        r2c_load(xr, xi, w2, row, B, 0, a.tw, lds, ltw, tid0);
-        r2c_stages<SGN, false>(xr, xi, w2, lds, ltw, tid0);
-        __syncthreads();
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) lds[(jt + jj * TPG) * G + g] = make_double2(xr[jj], xi[jj]);
-        __syncthreads();
-        if (g != 0) return;
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) {
-            const unsigned u = jt + jj * TPG, k = u * B;
-            const double2 zk = make_double2(xr[jj], xi[jj]);
-            if (u == 0) {
-                X[0] = make_double2(zk.x + zk.y, 0.0);
-                X[h] = make_double2(zk.x - zk.y, 0.0);
-            } else {
-                const double2 zh = lds[(P - u) * G];
-                double re, im;
-                r8::r2c_pair(zk, zh, w2t[k], re, im);
-                X[k] = make_double2(re, im);
-                X[N - k] = make_double2(re, -im);
-            }
-        }
-        return;
-    }
-    const unsigned j0 = s * T, j1 = min(j0 + T, B / 16), len = j1 - j0;
-    /* a.tile_major == 2: the walk starts at tile o of its segment and wraps (two chains:
-     * [j0+o, j1) then [j0, j0+o)), o from the row, so the workgroups of one XCD that share a
-     * segment (and its twiddles, from L2) read and write at different offsets of their rows --
-     * rows lie 32 MiB apart, so equal offsets would land in the same DRAM channels */
-    /* tile_major >= 3: only tile_major - 1 rotation classes, evenly spaced, so groups of
-     * workgroups share a tile (and its twiddles) at the same time */
-    const unsigned nrot = a.tile_major >= 3 ? (unsigned)a.tile_major - 1 : 0u;
-    const unsigned o = len == 0 ? 0u
-                     : a.tile_major == 2 ? (b * 7u) % len
-                     : nrot ? ((b % nrot) * len) / nrot : 0u;
-    R2cBuf A, Bf;
-    /* phase trace (a.dbg): thread 0 sums 100 MHz ticks per phase -- [0] tile pairs, [1] hi
-     * twiddles + stages, [2] lo twiddles + stages, [3] pairs + stores */
-    unsigned tr1 = 0, tr2 = 0, tr3 = 0, tk = TRC ? (unsigned)__builtin_amdgcn_s_memrealtime() : 0u;
-#define R2C_MARK(acc)                                                         \
-    if constexpr (TRC) {                                                      \
-        const unsigned tn = (unsigned)__builtin_amdgcn_s_memrealtime();       \
-        acc += tn - tk;                                                       \
-        tk = tn;                                                              \
-    }
-    r2cw2_issue<P_TWS>(A, row, B, B - 8 * (j0 + o) - 8, a.tw, tid0); /* hi of the first tile */
-#pragma unroll 1
-    for (unsigned jr = 0; jr < len; jr++) {
-        unsigned tid = tid0;
-        asm volatile("" : "+v"(tid));
-        const unsigned g = tid & 7, jt = tid >> 3;
-        const unsigned j = j0 + (o + jr) % len;
-        const unsigned qlo = 8 * j + 1;
-        r2cw2_issue<P_TWS>(Bf, row, B, qlo, a.tw, tid); /* lo(j) loads while hi(j) is transformed */
-        double2 w2[7];
-        /* ---- hi(j), in place in A */
-        r2cw2_tw(A, w2, lds, ltw, tid);
-        r2c_stages<SGN, false>(A.r, A.i, w2, lds, ltw, tid);
-        R2C_MARK(tr1)
-        double him[8];
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) him[jj] = A.i[jj];
-        /* ---- lo(j), in place in Bf */
-        r2cw2_tw(Bf, w2, lds, ltw, tid);
-
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) ld[4096 + (jt + jj * TPG) * G + g] = A.r[jj]; /* hi real parts wait here */
-        {   /* the next tile's hi loads while lo(j) is transformed; unconditional (the last tile
-             * reloads itself) */
-            const unsigned jn = jr + 1 < len ? j0 + (o + jr + 1) % len : j;
-            r2cw2_issue<P_TWS>(A, row, B, B - 8 * jn - 8, a.tw, tid);
-        }
-        r2c_stages<SGN, true>(Bf.r, Bf.i, w2, lds, ltw, tid);
-        R2C_MARK(tr2)
-        __syncthreads();
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) ld[(jt + jj * TPG) * G + g] = him[jj];
-        __syncthreads();
-        /* ---- pairs: X[N-k], X[h-k] aligned; X[k], X[h+k] shifted one lane onto line [8j, 8j+8) */
-        const bool cstart = jr == 0 || j == j0; /* a chain starts: no carry for this line */
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) {
-            const unsigned u = jt + jj * TPG, k = u * B + qlo + g, hk = h - k;
-            const unsigned sl = (P - 1 - u) * G + (7 - g);
-            const double2 zk = make_double2(Bf.r[jj], Bf.i[jj]), zh = make_double2(ld[4096 + sl], ld[sl]);
-            double re, im, re2, im2;
-            const double2 wk = P_TW2 ? w2t[tid0 & 63] : w2t[k];
-            const double2 whk = P_TW2 ? w2t[(tid0 & 63) + 64] : w2t[hk];
-            r8::r2c_pair(zk, zh, wk, re, im);
-            r8::r2c_pair(zh, zk, whk, re2, im2);
-            X[N - k] = make_double2(re, -im);
-            X[hk] = make_double2(re2, im2);
-            const double2 va = grp_shift<-1>(make_double2(re, im)), vb = grp_shift<-1>(make_double2(re2, -im2));
-            const unsigned p = u * B + 8 * j + g;
-            if (g != 0) {
-                X[p] = va;
-                X[h + p] = vb;
-            } else {
-                if (!cstart) {
-                    X[p] = cry[u];
-                    X[h + p] = cry[512 + u];
-                } else if (jr != 0 && j1 < B / 16) { /* the first chain's carry: bin 8*j1 */
-                    X[u * B + 8 * j1] = cry[u];
-                    X[h + u * B + 8 * j1] = cry[512 + u];
-                }
-                cry[u] = va;
-                cry[512 + u] = vb;
-            }
-        }
-        R2C_MARK(tr3)
-    }
-#undef R2C_MARK
-    if (TRC && tid0 == 0) {
-        unsigned *d = a.dbg + blockIdx.x * 4;
-        d[0] = len;
-        d[1] = tr1;
-        d[2] = tr2;
-        d[3] = tr3;
-    }
-    /* the last chain's carry: bin 8*(j0+o), or 8*j1 without rotation (at the row's last tile,
-     * column B/2, already written by the aligned streams) */
-    const unsigned jend = o > 0 ? j0 + o : j1;
-    if (len > 0 && jend < B / 16 && (tid0 & 7) == 0) {
-        const unsigned jt = tid0 >> 3;
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) {
-            const unsigned u = jt + jj * TPG, p = u * B + 8 * jend;
-            X[p] = cry[u];
-            X[h + p] = cry[512 + u];
-        }
-    }
-}
-
 /* ------------------------------------------------------------------ r2c split, two walks per CU
- * k_r2c_walk2's split walk (whole-line stores through the one-lane shift and the carried entry)
- * without its software pipeline, sized so that TWO workgroups share a CU (round 4): at most 128
- * VGPRs and 80 KiB of LDS -- the split image (32 KiB), the hi tile's real parts (32 KiB) and the
- * carry (16 KiB).  One tile buffer per thread; the stage-0 / stage-1 twiddle runs are read from
- * the plan's table in global memory (L2 / Infinity-Cache hits) instead of an LDS copy, the
- * stage-1 run issued behind stage 0.  A CU then overlaps one walk's loads and store drains with
- * the other walk's stages, where the one-per-CU walk serialises them in its own phase order
- * (every load issued after a store burst waits for that burst: vmcnt is in order). */
+ * k_r2c_fused's sequential hi / lo tiles, but a workgroup walks T consecutive tile pairs of a
+ * row and the lo thread writes all four streams of its pair: X[N-k] and X[h-k] lie on whole
+ * 128-B lines; X[k] and X[h+k] sit one entry off them, so they are shifted one lane inside each
+ * 8-lane group and the entry that belongs to the next line is carried to the next tile (LDS,
+ * same thread).  Every output line is then written whole by one workgroup.  Sized so that TWO
+ * workgroups share a CU: at most 128 VGPRs and 80 KiB of LDS -- the split image (32 KiB), the
+ * hi tile's real parts (32 KiB) and the carry (16 KiB).  One tile buffer per thread; the
+ * stage-0 / stage-1 twiddle runs are read from the plan's table in global memory (L2 /
+ * Infinity-Cache hits) instead of an LDS copy, the stage-1 run issued behind stage 0.  A CU then
+ * overlaps one walk's loads and store drains with the other walk's stages (every load issued
+ * after a store burst waits for that burst: vmcnt is in order).  The software-pipelined
+ * one-per-CU walk it replaced ran 24.23 against 22.25 ms per 512 rows. */
 constexpr int R2CW1_LDS = (512 * 8 + 1024) * 16;
 
 /* a run of 7 twiddles at table index idx (stage 0: B - 1 + 7q; stage 1: 8B - 1 + 7(q + B kl)) */
@@ -707,34 +488,6 @@ __device__ __forceinline__ void redistribute_at(double2 (&w)[7], double2 *region
     for (int i = 0; i < 7; i++) w[i] = reg[(lane & 7) * 7 + i];
 }
 
-/* PROBE (timing probes of k_r2c_walk1, -DHSFFT_DEV_PROBES builds only; results wrong): bit 0 no
- * twiddle2 loads, bit 1 no stage twiddle loads, bit 2 no stage arithmetic (the twiddles are
- * folded in with one add each so that their loads stay), bit 3 no exchanges / redistribution,
- * bit 4 no output stores (kept behind a condition that is false at run time) */
-template <int PROBE>
-__device__ __forceinline__ void p_tw_run(double2 (&w)[7], const double2 *tw, unsigned idx)
-{
-    if constexpr (PROBE & 2) {
-#pragma unroll
-        for (int i = 0; i < 7; i++) w[i] = make_double2(0.5 + i, 0.25 - i);
-    } else {
-        tw_run(w, tw, idx);
-    }
-}
-template <int PROBE, int SGN>
-__device__ __forceinline__ void p_stage(double (&xr)[8], double (&xi)[8], const double2 (&w)[7])
-{
-    if constexpr (PROBE & 4) {
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-            xr[i + 1] += w[i].x;
-            xi[i + 1] += w[i].y;
-        }
-    } else {
-        stage<8, SGN>(xr, xi, w, false);
-    }
-}
-
 /* one tile's row loads */
 __device__ __forceinline__ void w1_rows(double (&xr)[8], double (&xi)[8], const double2 *row, unsigned B, unsigned q0,
                                         unsigned tid)
@@ -751,12 +504,11 @@ __device__ __forceinline__ void w1_rows(double (&xr)[8], double (&xi)[8], const 
 }
 
 /* one tile's row loads and its stage-0 run (registers) */
-template <int PROBE = 0>
 __device__ __forceinline__ void w1_load(double (&xr)[8], double (&xi)[8], double2 (&w)[7], const double2 *row,
                                         unsigned B, unsigned q0, const double2 *tw, unsigned tid)
 {
     w1_rows(xr, xi, row, B, q0, tid);
-    p_tw_run<PROBE>(w, tw, B - 1 + 7 * (q0 + (tid & 7)));
+    tw_run(w, tw, B - 1 + 7 * (q0 + (tid & 7)));
 }
 
 /* the tile's three stages with one twiddle run live at a time (<= 128 VGPRs with the hi tile's
@@ -764,7 +516,7 @@ __device__ __forceinline__ void w1_load(double (&xr)[8], double (&xi)[8], double
  * the coalesced stage-2 run after the second and redistributed through the
  * image's first half (waves 0-3, then 4-7: the second half may hold the hi tile's real parts);
  * split exchanges through doubles [0, 4096) */
-template <int SGN, int PROBE = 0>
+template <int SGN>
 __device__ __forceinline__ void w1_stages(double (&xr)[8], double (&xi)[8], double2 (&w)[7], double2 *lds,
                                           const double2 *tw, unsigned B, unsigned q0, unsigned tid0)
 {
@@ -772,54 +524,37 @@ __device__ __forceinline__ void w1_stages(double (&xr)[8], double (&xi)[8], doub
     unsigned tid = tid0;
     asm volatile("" : "+v"(tid));
     const unsigned g = tid & 7, jt = tid >> 3;
-    p_stage<PROBE, SGN>(xr, xi, w);
-    if constexpr (!(PROBE & 8)) r8::exchange<8, 1, 8, TPG, P, G, true>(xr, xi, lds, jt, g);
-    p_tw_run<PROBE>(w, tw, 8 * B - 1 + 7 * (q0 + g + B * (jt & 7))); /* after the exchange: issued
-                                                                        * earlier, its 28 VGPRs spill */
-    p_stage<PROBE, SGN>(xr, xi, w);
-    if constexpr (!(PROBE & 8)) r8::exchange<8, 8, 8, TPG, P, G, true>(xr, xi, lds, jt, g); /* ends with a barrier */
-    if constexpr (!(PROBE & 2)) {
-        r8::Args ta;
-        ta.tw = tw;
-        ta.B = B;
-        r8::load_tw_co<64>(w, ta, (int)jt, q0);
-    } else {
-        p_tw_run<PROBE>(w, tw, 0);
-    }
-    if constexpr (!(PROBE & 8)) {
-        const unsigned wave = tid0 >> 6;
-        if (wave < 4) redistribute_at(w, lds + wave * 448);
-        __syncthreads();
-        if (wave >= 4) redistribute_at(w, lds + (wave - 4) * 448);
-    }
-    p_stage<PROBE, SGN>(xr, xi, w);
+    stage<8, SGN>(xr, xi, w, false);
+    r8::exchange<8, 1, 8, TPG, P, G, true>(xr, xi, lds, jt, g);
+    tw_run(w, tw, 8 * B - 1 + 7 * (q0 + g + B * (jt & 7))); /* after the exchange: issued earlier,
+                                                               * its 28 VGPRs spill */
+    stage<8, SGN>(xr, xi, w, false);
+    r8::exchange<8, 8, 8, TPG, P, G, true>(xr, xi, lds, jt, g); /* ends with a barrier */
+    r8::Args ta;
+    ta.tw = tw;
+    ta.B = B;
+    r8::load_tw_co<64>(w, ta, (int)jt, q0);
+    const unsigned wave = tid0 >> 6;
+    if (wave < 4) redistribute_at(w, lds + wave * 448);
+    __syncthreads();
+    if (wave >= 4) redistribute_at(w, lds + (wave - 4) * 448);
+    stage<8, SGN>(xr, xi, w, false);
 }
 
-#ifdef HSFFT_DEV_PROBES
-/* this workgroup's CU: XCD, shader engine, shader array and CU fields of HW_ID (< 2048) */
-__device__ __forceinline__ unsigned cu_slot()
-{
-    const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));   /* HW_REG_HW_ID */
-    const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (15 << 11)); /* HW_REG_XCC_ID */
-    return ((xcc & 7) << 8) | (((hw >> 13) & 7) << 5) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 15);
-}
-#endif
-
-/* PFH: the next tile's hi rows are loaded at the start of this tile's pairs phase, i.e. before
- * its store burst, so waiting for them does not wait for the stores (vmcnt is in order); PFL:
- * the lo rows are loaded at the start of the hi phase, while the hi tile is transformed.
- * STOK (development build, round 5 -- the test of the store-burst alignment hypothesis): the
- * two walks a CU holds never have store bursts in flight together.  A per-CU token word
- * (a.dbg[cu_slot()], zero when free) is taken by thread 0 before the pairs phase and returned
- * once the phase's stores have drained (1) or once they are issued (2); the wait is bounded
- * (50 us, about one tile pair), after which the walk stores without the token */
-template <int SGN, bool PFH = false, bool PFL = false, int PROBE = 0, int STOK = 0>
+/* The next tile's hi rows are loaded at the start of this tile's pairs phase, i.e. before its
+ * store burst, so waiting for them does not wait for the stores (vmcnt is in order): 20.00 vs
+ * 20.15 ms per 512 rows without that prefetch.  Loading the lo rows during the hi phase as
+ * well (20.11), and keeping the two walks of a CU from storing at the same time (a per-CU
+ * token: 5.8 % slower), both lost (rounds 4 and 5). */
+template <int SGN>
 __global__ __launch_bounds__(512, 4) void k_r2c_walk1(Args a, unsigned h, unsigned T, unsigned W)
 {
     constexpr int P = 512, TPG = 64, G = 8;
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
     double2 *cry = lds + P * G;
     double *ld = reinterpret_cast<double *>(lds); /* [0, 4096): split image / hi imag, [4096, 8192): hi real */
+    /* a.tile_major != 0: consecutive blocks (one XCD) take the same walk segment of consecutive
+     * rows, so the segment's twiddle runs and twiddle2 slice are read from that XCD's L2 */
     const unsigned blk = xcd_remap(blockIdx.x), nb = (unsigned)a.batch;
     const unsigned b = a.tile_major ? blk % nb : blk / (W + 1), s = a.tile_major ? blk / nb : blk % (W + 1);
     const unsigned tid0 = threadIdx.x, B = (unsigned)a.B, N = 2 * h;
@@ -855,15 +590,19 @@ __global__ __launch_bounds__(512, 4) void k_r2c_walk1(Args a, unsigned h, unsign
         }
         return;
     }
-    /* walk segment, rotation and carry chains exactly as k_r2c_walk2 */
     const unsigned j0 = s * T, j1 = min(j0 + T, B / 16), len = j1 - j0;
+    /* a.tile_major == 2: the walk starts at tile o of its segment and wraps (two chains:
+     * [j0+o, j1) then [j0, j0+o)), o from the row, so the workgroups of one XCD that share a
+     * segment (and its twiddles, from L2) read and write at different offsets of their rows --
+     * rows lie 32 MiB apart, so equal offsets would land in the same DRAM channels.
+     * tile_major >= 3: only tile_major - 1 rotation classes, evenly spaced, so groups of
+     * workgroups share a tile (and its twiddles) at the same time */
     const unsigned nrot = a.tile_major >= 3 ? (unsigned)a.tile_major - 1 : 0u;
     const unsigned o = len == 0 ? 0u
                      : a.tile_major == 2 ? (b * 7u) % len
                      : nrot ? ((b % nrot) * len) / nrot : 0u;
-    double pr[8], pi[8]; /* PFH: the next hi tile's rows */
-    if constexpr (PFH)
-        if (len > 0) w1_rows(pr, pi, row, B, B - 8 * (j0 + o) - 8, tid0);
+    double pr[8], pi[8]; /* the next hi tile's rows */
+    if (len > 0) w1_rows(pr, pi, row, B, B - 8 * (j0 + o) - 8, tid0);
 #pragma unroll 1
     for (unsigned jr = 0; jr < len; jr++) {
         unsigned tid = tid0;
@@ -874,102 +613,50 @@ __global__ __launch_bounds__(512, 4) void k_r2c_walk1(Args a, unsigned h, unsign
         double xr[8], xi[8], him[8];
         double2 w[7];
         /* ---- hi(j) */
-        if constexpr (PFH) {
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
-                xr[i] = pr[i];
-                xi[i] = pi[i];
-            }
-            p_tw_run<PROBE>(w, a.tw, B - 1 + 7 * (qhi + g));
-        } else {
-            w1_load<PROBE>(xr, xi, w, row, B, qhi, a.tw, tid);
+        for (int i = 0; i < 8; i++) {
+            xr[i] = pr[i];
+            xi[i] = pi[i];
         }
-        double lr[8], li[8]; /* PFL: the lo tile's rows */
-        if constexpr (PFL) w1_rows(lr, li, row, B, qlo, tid);
+        tw_run(w, a.tw, B - 1 + 7 * (qhi + g));
         __syncthreads(); /* the previous pairs phase has read the image */
-        w1_stages<SGN, PROBE>(xr, xi, w, lds, a.tw, B, qhi, tid);
+        w1_stages<SGN>(xr, xi, w, lds, a.tw, B, qhi, tid);
 #pragma unroll
         for (int jj = 0; jj < 8; jj++) {
             ld[4096 + (jt + jj * TPG) * G + g] = xr[jj]; /* hi real parts wait in the image's second half */
             him[jj] = xi[jj];
         }
         /* ---- lo(j) */
-        if constexpr (PFL) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                xr[i] = lr[i];
-                xi[i] = li[i];
-            }
-            p_tw_run<PROBE>(w, a.tw, B - 1 + 7 * (qlo + g));
-        } else {
-            w1_load<PROBE>(xr, xi, w, row, B, qlo, a.tw, tid);
-        }
+        w1_load(xr, xi, w, row, B, qlo, a.tw, tid);
         __syncthreads(); /* every wave's hi stage-2 twiddles are read back from the image */
-        w1_stages<SGN, PROBE>(xr, xi, w, lds, a.tw, B, qlo, tid);
+        w1_stages<SGN>(xr, xi, w, lds, a.tw, B, qlo, tid);
         __syncthreads();
 #pragma unroll
         for (int jj = 0; jj < 8; jj++) ld[(jt + jj * TPG) * G + g] = him[jj];
         __syncthreads();
         /* ---- pairs: X[N-k], X[h-k] aligned; X[k], X[h+k] shifted one lane onto line [8j, 8j+8) */
-#ifdef HSFFT_DEV_PROBES
-        bool own = false;
-        unsigned *tok = nullptr;
-        if constexpr (STOK != 0) {
-            tok = a.dbg + cu_slot();
-            if (tid0 == 0) {
-                const unsigned t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
-                unsigned tries = 0;
-                for (;; tries++) {
-                    if (atomicCAS(tok, 0u, blockIdx.x + 1u) == 0u) {
-                        own = true;
-                        break;
-                    }
-                    if ((unsigned)__builtin_amdgcn_s_memrealtime() - t0 > 5000u) break;
-                    __builtin_amdgcn_s_sleep(2);
-                }
-                /* statistics after the 2048 token words: pairs phases, phases that waited, timeouts,
-                 * 10-ns ticks waited */
-                if (a.tiles_q) {
-                    atomicAdd(a.dbg + 2048, 1u);
-                    if (tries) {
-                        atomicAdd(a.dbg + 2049, 1u);
-                        atomicAdd(a.dbg + 2051, (unsigned)__builtin_amdgcn_s_memrealtime() - t0);
-                    }
-                    if (!own) atomicAdd(a.dbg + 2050, 1u);
-                }
-            }
-            __syncthreads();
-        }
-#endif
-        if constexpr (PFH) { /* unconditional: the last tile reloads itself */
-            const unsigned jn = jr + 1 < len ? j0 + (o + jr + 1) % len : j;
-            w1_rows(pr, pi, row, B, B - 8 * jn - 8, tid);
-        }
-        const bool cstart = jr == 0 || j == j0;
+        /* the next tile's hi rows, before this phase's stores; unconditional: the last tile
+         * reloads itself */
+        const unsigned jn = jr + 1 < len ? j0 + (o + jr + 1) % len : j;
+        w1_rows(pr, pi, row, B, B - 8 * jn - 8, tid);
+        const bool cstart = jr == 0 || j == j0; /* a chain starts: no carry for this line */
 #pragma unroll
         for (int jj = 0; jj < 8; jj++) {
             const unsigned u = jt + jj * TPG, k = u * B + qlo + g, hk = h - k;
             const unsigned sl = (P - 1 - u) * G + (7 - g);
             const double2 zk = make_double2(xr[jj], xi[jj]), zh = make_double2(ld[4096 + sl], ld[sl]);
             double re, im, re2, im2;
-            const double2 wk = (PROBE & 1) ? make_double2(0.5, 0.25) : w2t[k];
-            const double2 whk = (PROBE & 1) ? make_double2(0.25, 0.5) : w2t[hk];
-            r8::r2c_pair(zk, zh, wk, re, im);
-            r8::r2c_pair(zh, zk, whk, re2, im2);
-            const bool st = !(PROBE & 16) || h == 0; /* h > 0 always: the probe stores nothing */
-            if (st) {
-                X[N - k] = make_double2(re, -im);
-                X[hk] = make_double2(re2, im2);
-            }
+            r8::r2c_pair(zk, zh, w2t[k], re, im);
+            r8::r2c_pair(zh, zk, w2t[hk], re2, im2);
+            X[N - k] = make_double2(re, -im);
+            X[hk] = make_double2(re2, im2);
             const double2 va = grp_shift<-1>(make_double2(re, im)), vb = grp_shift<-1>(make_double2(re2, -im2));
             const unsigned p = u * B + 8 * j + g;
             if (g != 0) {
-                if (st) {
-                    X[p] = va;
-                    X[h + p] = vb;
-                }
+                X[p] = va;
+                X[h + p] = vb;
             } else {
-                if (!cstart && st) {
+                if (!cstart) {
                     X[p] = cry[u];
                     X[h + p] = cry[512 + u];
                 } else if (jr != 0 && j1 < B / 16) { /* the first chain's carry: bin 8*j1 */
@@ -980,14 +667,9 @@ __global__ __launch_bounds__(512, 4) void k_r2c_walk1(Args a, unsigned h, unsign
                 cry[512 + u] = vb;
             }
         }
-#ifdef HSFFT_DEV_PROBES
-        if constexpr (STOK != 0) {
-            if constexpr (STOK == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid0 == 0 && own) atomicCAS(tok, blockIdx.x + 1u, 0u);
-        }
-#endif
     }
+    /* the last chain's carry: bin 8*(j0+o), or 8*j1 without rotation (at the row's last tile,
+     * column B/2, already written by the aligned streams) */
     const unsigned jend = o > 0 ? j0 + o : j1;
     if (len > 0 && jend < B / 16 && (tid0 & 7) == 0) {
         const unsigned jt = tid0 >> 3;
@@ -1019,129 +701,21 @@ inline int launch_r2c_fused(const void *Z, long long zdist, void *X, long long x
     a.B = B;
     a.batch = batch;
     a.tiles = a.tiles_q = B / 16 + 1;
-    /* default: k_r2c_walk2, walks of 8 tile pairs, segment-major, the walk start of row b at
-     * tile b % 8 (HSFFT_R2C_ORDER=9: 8 rotation classes).  Interleaved on one box (two passes
-     * each, GSamples/s): 105.8 / 105.8 vs 103.5-104.3 for the (b*7) % 16 rotation with walks of
-     * 16 (ORDER=2), 99.7-99.8 row-major with walks of 32 (0), 98.4-98.8 with 4 classes and 94.3-94.7
-     * with 2 (ORDER=5, 3: FETCH 32.3 / 29.3 GB per 512 rows, the twiddles mostly from L2, yet
-     * slower: workgroups that read the same lines at the same time contend); plain
-     * segment-major (1) 88.7-90.8 elsewhere; HSFFT_R2C_WALK=0 (and the compact layout):
-     * k_r2c_fused */
-    /* default (round 4): k_r2c_walk1 -- two walks per CU, walks of 32 tile pairs, 8 rotation
-     * classes; in-process A/B per 512 rows against k_r2c_walk2 (walks of 8): 20.40 vs 20.31 ms on a
-     * fast-write allocation, 20.97 vs 22.20 on a medium one, 22.25-23.60 vs 24.23-25.77 on three
-     * slow ones (profiles/r04d-f_*).  HSFFT_R2C_WALK=2: walk2; 0: k_r2c_fused */
-    /* product: k_r2c_walk1 (default) or, HSFFT_R2C_WALK=0, k_r2c_fused -- the independent
-     * schedule the every-word test compares against, and the compact layout's kernel.  The
-     * measured-slower walks (k_r2c_walk2, walk1's other prefetch forms, the other walk orders,
-     * the phase trace) are compiled only into the development build (-DHSFFT_DEV_PROBES) */
-    const int walk = env("HSFFT_R2C_WALK", 3) != 0 ? 3 : 0;
-    if (!compact && walk != 0) {
-#ifdef HSFFT_DEV_PROBES
-        const bool w2 = env("HSFFT_R2C_WALK", 3) == 2 || env("HSFFT_R2C_DEBUG", 0) != 0;
-        const int wt_dflt = w2 ? 8 : 32;
-#else
-        const int wt_dflt = 32;
-#endif
-        const long long T = env("HSFFT_R2C_WT", wt_dflt) > 0 ? env("HSFFT_R2C_WT", wt_dflt) : wt_dflt,
-                        W = (B / 16 + T - 1) / T;
+    /* k_r2c_walk1 is the default: walks of HSFFT_R2C_WT tile pairs (default 32), segment-major,
+     * the walk start of row b in one of 8 rotation classes (a.tile_major = 9; DESIGN.md §5, rounds
+     * 3 and 4, has the other orders and walk lengths).  HSFFT_R2C_WALK=0 and the compact layout
+     * take k_r2c_fused -- the independent schedule the every-word test compares against */
+    if (!compact && env("HSFFT_R2C_WALK", 3) != 0) {
+        const int wt = env("HSFFT_R2C_WT", 32);
+        const long long T = wt > 0 ? wt : 32, W = (B / 16 + T - 1) / T;
         const long long grid = (W + 1) * (long long)batch;
         if (grid <= 0 || grid > 0x7fffffffLL) return -1;
-        typedef void (*wfn)(Args, unsigned, unsigned, unsigned);
-        /* k_r2c_walk1<SGN, PFH = true>: the next hi tile's rows loaded before the pairs phase's
-         * stores, 20.00 vs 20.15 ms per 512 rows in-process (profiles/r04i_i_c5.txt) */
-        wfn fw = sgn == 1 ? k_r2c_walk1<1, true> : k_r2c_walk1<-1, true>;
-        int lds_bytes = R2CW1_LDS;
-        a.tile_major = 9; /* 8 rotation classes */
-        bool dbg = false, stok_stats = false;
-#ifdef HSFFT_DEV_PROBES
-        {
-            /* development build: HSFFT_R2C_WALK=2 k_r2c_walk2 (round 3's one-per-CU walk, walks of
-             * 8 by default); HSFFT_R2C_DEBUG=1 its phase trace; HSFFT_R2C_PROBE (timing only, results
-             * wrong): 1 no twiddle2 traffic, 2 no stage-2 twiddle traffic, 3 neither */
-            dbg = env("HSFFT_R2C_DEBUG", 0) != 0;
-            if (w2) {
-                static const wfn fws[2][8] = {
-                    {k_r2c_walk2<1, 0>, k_r2c_walk2<1, 1>, k_r2c_walk2<1, 2>, k_r2c_walk2<1, 3>, k_r2c_walk2<1, 4>,
-                     k_r2c_walk2<1, 5>, k_r2c_walk2<1, 6>, k_r2c_walk2<1, 7>},
-                    {k_r2c_walk2<-1, 0>, k_r2c_walk2<-1, 1>, k_r2c_walk2<-1, 2>, k_r2c_walk2<-1, 3>, k_r2c_walk2<-1, 4>,
-                     k_r2c_walk2<-1, 5>, k_r2c_walk2<-1, 6>, k_r2c_walk2<-1, 7>}};
-                fw = fws[sgn == 1 ? 0 : 1][(dbg ? 1 : 0) | (env("HSFFT_R2C_PROBE", 0) & 3) << 1];
-                lds_bytes = R2CW2_LDS;
-            } else {
-                /* walk1's other prefetch forms: HSFFT_R2C_PFH 0 none, 2 the lo rows with the hi phase,
-                 * 3 both (20.11 vs 20.00 ms, profiles/r04i_i_c5.txt) */
-                switch (env("HSFFT_R2C_PFH", 1)) {
-                case 0: fw = sgn == 1 ? k_r2c_walk1<1> : k_r2c_walk1<-1>; break;
-                case 2: fw = sgn == 1 ? k_r2c_walk1<1, false, true> : k_r2c_walk1<-1, false, true>; break;
-                case 3: fw = sgn == 1 ? k_r2c_walk1<1, true, true> : k_r2c_walk1<-1, true, true>; break;
-                default: break;
-                }
-                /* HSFFT_R2C_W1PROBE (timing only, results wrong; the default PFH walk, sgn 1): see PROBE */
-                switch (sgn == 1 ? env("HSFFT_R2C_W1PROBE", 0) : 0) {
-                case 3: fw = k_r2c_walk1<1, true, false, 3>; break;
-                case 4: fw = k_r2c_walk1<1, true, false, 4>; break;
-                case 8: fw = k_r2c_walk1<1, true, false, 8>; break;
-                case 12: fw = k_r2c_walk1<1, true, false, 12>; break;
-                case 15: fw = k_r2c_walk1<1, true, false, 15>; break;
-                case 16: fw = k_r2c_walk1<1, true, false, 16>; break;
-                case 31: fw = k_r2c_walk1<1, true, false, 31>; break;
-                default: break;
-                }
-                /* HSFFT_R2C_STOK 1 / 2: the per-CU store token (see k_r2c_walk1), bit-exact */
-                const int stok = env("HSFFT_R2C_STOK", 0);
-                if (stok == 1 || stok == 2) {
-                    static unsigned *s_tok = nullptr;
-                    if (!s_tok) {
-                        HCHK(hipMalloc((void **)&s_tok, 2052 * sizeof(unsigned)));
-                        HCHK(hipMemset(s_tok, 0, 2052 * sizeof(unsigned)));
-                    }
-                    a.dbg = s_tok;
-                    stok_stats = env("HSFFT_R2C_STOK_STATS", 0) != 0;
-                    a.tiles_q = stok_stats ? 1 : 0; /* walk1 does not read tiles_q otherwise */
-                    fw = stok == 1 ? (sgn == 1 ? k_r2c_walk1<1, true, false, 0, 1> : k_r2c_walk1<-1, true, false, 0, 1>)
-                                   : (sgn == 1 ? k_r2c_walk1<1, true, false, 0, 2> : k_r2c_walk1<-1, true, false, 0, 2>);
-                }
-            }
-            /* walk orders: 0 row-major, 1 segment-major, 2 rotated, >= 3 rotation classes */
-            a.tile_major = env("HSFFT_R2C_ORDER", 9);
-        }
-#endif
-        static unsigned *s_dbg = nullptr;
-        static long long s_dbg_n = 0;
-        if (dbg) {
-            if (s_dbg_n < grid) {
-                if (s_dbg) HCHK(hipFree(s_dbg));
-                HCHK(hipMalloc((void **)&s_dbg, (size_t)grid * 4 * sizeof(unsigned)));
-                s_dbg_n = grid;
-            }
-            HCHK(hipMemsetAsync(s_dbg, 0, (size_t)grid * 4 * sizeof(unsigned), st));
-            a.dbg = s_dbg;
-        }
-        HCHK(hipFuncSetAttribute((const void *)fw, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        hipLaunchKernelGGL(fw, dim3((unsigned)grid), dim3(512), lds_bytes, st, a, (unsigned)h, (unsigned)T, (unsigned)W);
+        void (*fw)(Args, unsigned, unsigned, unsigned) = sgn == 1 ? k_r2c_walk1<1> : k_r2c_walk1<-1>;
+        a.tile_major = 9;
+        HCHK(hipFuncSetAttribute((const void *)fw, hipFuncAttributeMaxDynamicSharedMemorySize, R2CW1_LDS));
+        hipLaunchKernelGGL(fw, dim3((unsigned)grid), dim3(512), R2CW1_LDS, st, a, (unsigned)h, (unsigned)T,
+                           (unsigned)W);
         HCHK(hipGetLastError());
-        if (stok_stats) { /* development build: the store token's statistics of this launch */
-            unsigned hs[4];
-            HCHK(hipMemcpyAsync(hs, a.dbg + 2048, sizeof hs, hipMemcpyDeviceToHost, st));
-            HCHK(hipStreamSynchronize(st));
-            HCHK(hipMemsetAsync(a.dbg + 2048, 0, sizeof hs, st));
-            fprintf(stderr, "r2c store token: %u pairs phases, %u waited (mean %.2f us), %u timed out\n", hs[0], hs[1],
-                    hs[1] ? hs[3] / 100.0 / hs[1] : 0.0, hs[2]);
-        }
-        if (dbg) { /* mean us per tile pair of the walking workgroups */
-            unsigned *hb = (unsigned *)malloc((size_t)grid * 4 * sizeof(unsigned));
-            if (!hb) return -1;
-            HCHK(hipMemcpyAsync(hb, s_dbg, (size_t)grid * 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-            HCHK(hipStreamSynchronize(st));
-            double t[4] = {0, 0, 0, 0};
-            for (long long w = 0; w < grid; w++)
-                for (int i = 0; i < 4; i++) t[i] += hb[w * 4 + i];
-            free(hb);
-            const double n = t[0] > 0 ? t[0] : 1;
-            fprintf(stderr, "r2c_walk2: tile pairs %.0f  us per tile pair: hi %.2f lo %.2f pairs+stores %.2f\n", t[0],
-                    t[1] / n / 100.0, t[2] / n / 100.0, t[3] / n / 100.0);
-        }
         return 0;
     }
     const long long grid = a.tiles * (long long)batch;
@@ -1247,12 +821,6 @@ inline int launch(const hsd_pass *p, const hsd_launch *l, hipStream_t st)
     size_t lds = 0;
     kfn fn = pick(p, l, &G, &TL, &threads, &lds);
     if (!fn) return 1;
-#ifdef HSFFT_DEV_PROBES
-    {
-        const unsigned m = env("HSFFT_PFA_PROBE", 0) ? 7u : 0xffffffffu;
-        HCHK(hipMemcpyToSymbol(HIP_SYMBOL(pf_probe_twmask), &m, sizeof m));
-    }
-#endif
     Args a;
     memset(&a, 0, sizeof a);
     a.in = (const double2 *)l->in;

@@ -26,7 +26,7 @@ struct Args {
     int xcd_groups;   /* >0: remap block ids so that consecutive tiles share an XCD */
     int tile_major;   /* 1: block order tile-major (all rows of a tile adjacent) */
     long long batch;
-    unsigned *dbg;    /* optional per-workgroup phase trace (k_r2c_walk2, HSFFT_R2C_DEBUG) */
+    unsigned *dbg;    /* unused by the pf kernels; mr and bxc have their own */
     unsigned *done;   /* k_pass launched as one workgroup: host completion word (hsd_launch) */
     unsigned done_val;
 };
@@ -163,14 +163,11 @@ constexpr Swz split_swz(int R, int LLOC, int G)
 template <int R, int LLOC, int G, bool SPLIT = false>
 __device__ __forceinline__ unsigned lds_slot(unsigned p)
 {
-#ifndef HSFFT_SPLIT_SWZ_R2 /* (experiment builds: -DHSFFT_SPLIT_SWZ_R2 keeps round 2's swizzle) */
     if constexpr (SPLIT) {
         constexpr Swz z = split_swz(R, LLOC, G);
         if constexpr (z.k > 0) return p ^ (((p >> z.s) & ((1u << z.k) - 1u)) << z.t);
         return p;
-    } else
-#endif
-    {
+    } else {
         if constexpr (LLOC == 1 && G < 8 && R > 1) return p ^ ((p / R) & (R - 1));
         return p;
     }
@@ -608,97 +605,6 @@ __device__ __forceinline__ void r2c_pair(double2 a, double2 c, double2 w, double
     re = (a.x + c.x + (t1 * w.x) + (t2 * w.y)) / 2.0;
     im = (a.y - c.y + (t2 * w.x) - (t1 * w.y)) / 2.0;
 }
-
-#ifdef HSFFT_DEV_PROBES /* round 1's split kernel: development build only (HSFFT_R2C_FUSE=2) */
-__global__ __launch_bounds__(512, 4) void k_r2c_last(Args a, long long h)
-{
-    constexpr int P = 512, TPG = 64, G = 8;
-    extern __shared__ __attribute__((aligned(16))) double2 lds[];
-    unsigned blk = blockIdx.x;
-    {
-        const unsigned nwg = gridDim.x, q8 = nwg / 8, r8 = nwg % 8, xcd = blk % 8;
-        blk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + blk / 8;
-    }
-    const unsigned tiles = (unsigned)a.tiles, b = blk / tiles, j = blk % tiles;
-    const int tid = threadIdx.x, g = tid % G, jt = tid / G;
-    const long long B = a.B, N = 2 * h;
-    const double2 *in = a.in + (long long)b * a.idist;
-    double2 *X = a.out + (long long)b * a.odist;
-    const double2 *w2 = a.saux;
-    double xr[8], xi[8];
-    if (j < tiles - 1) {
-        const long long qlo = 8 * (long long)j + 1, qhi = B - 8 * (long long)j - 8;
-        double hr[8], hi[8];
-        tile888(hr, hi, a, in, qhi, jt, g, lds);
-        tile888(xr, xi, a, in, qlo, jt, g, lds);
-        __syncthreads();
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) lds[(jt + jj * TPG) * G + g] = make_double2(hr[jj], hi[jj]);
-        __syncthreads();
-        const long long q = qlo + g;
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) {
-            const int u = jt + jj * TPG;
-            const long long k = u * B + q, hk = h - k;
-            const double2 zk = make_double2(xr[jj], xi[jj]), zh = lds[(P - 1 - u) * G + (7 - g)];
-            double re, im;
-            r2c_pair(zk, zh, w2[k], re, im);
-            X[k] = make_double2(re, im);
-            X[N - k] = make_double2(re, -im);
-            r2c_pair(zh, zk, w2[hk], re, im);
-            X[hk] = make_double2(re, im);
-            X[N - hk] = make_double2(re, -im);
-        }
-    } else { /* column 0: k = u*B pairs with (P-u)*B */
-        tile888(xr, xi, a, in, 0, jt, g, lds);
-        __syncthreads();
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) lds[(jt + jj * TPG) * G + g] = make_double2(xr[jj], xi[jj]);
-        __syncthreads();
-        if (g != 0) return;
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) {
-            const int u = jt + jj * TPG;
-            const long long k = u * B;
-            const double2 zk = make_double2(xr[jj], xi[jj]);
-            if (u == 0) {
-                X[0] = make_double2(zk.x + zk.y, 0.0);
-                X[h] = make_double2(zk.x - zk.y, 0.0);
-            } else {
-                const double2 zh = lds[(P - u) * G];
-                double re, im;
-                r2c_pair(zk, zh, w2[k], re, im);
-                X[k] = make_double2(re, im);
-                X[N - k] = make_double2(re, -im);
-            }
-        }
-    }
-}
-
-inline int launch_r2c_last(const void *Z, long long zdist, void *X, long long xdist, const void *tw, const void *w2,
-                           long long h, long long B, int batch, int sgn, hipStream_t st)
-{
-    if (B % 16 || B * 512 != h) return -1;
-    Args a;
-    memset(&a, 0, sizeof a);
-    a.in = (const double2 *)Z;
-    a.out = (double2 *)X;
-    a.tw = (const double2 *)tw;
-    a.saux = (const double2 *)w2;
-    a.idist = zdist;
-    a.odist = xdist;
-    a.A = 1;
-    a.B = B;
-    a.sgn = sgn;
-    a.batch = batch;
-    a.tiles = a.tiles_q = B / 16 + 1;
-    const long long grid = a.tiles * (long long)batch;
-    if (grid <= 0 || grid > 0x7fffffffLL) return -1;
-    hipLaunchKernelGGL(k_r2c_last, dim3((unsigned)grid), dim3(512), 512 * 8 * sizeof(double2), st, a, h);
-    HCHK(hipGetLastError());
-    return 0;
-}
-#endif
 
 typedef void (*kfn)(Args);
 

@@ -722,8 +722,7 @@ def test_r2c_walk1(n, sgn, wt, monkeypatch):
     (every tile a walk's first: partial first line, carry written at once), 5 (uneven walks, a
     short last walk), 4096 (one walk per row: the carry reaches column B/2); walk0: the
     one-tile-per-workgroup pf::k_r2c_fused (HSFFT_R2C_WALK=0).  Bit-exact vs the oracle, odd
-    batch, stale output buffer.  (The measured-slower walks -- k_r2c_walk2, walk1's other
-    prefetch forms and walk orders -- are in the development build: tests/dev/.)"""
+    batch, stale output buffer."""
     if wt == "walk0":
         monkeypatch.setenv("HSFFT_R2C_WALK", "0")
     else:

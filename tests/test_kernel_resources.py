@@ -18,6 +18,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(REPO, "mixed-radix-fast-fourier-transform_amd", "lib", "libhsfft.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 
+WALK1 = r"^_ZN2pf11k_r2c_walk1ILin?1EEE"  # pf::k_r2c_walk1<SGN>: the only form there is
+
 # (kernel-name regex on the mangled name, max VGPR spill dwords, max VGPRs, min waves per SIMD
 #  that the register allocation allows -- the occupancy each kernel's launch geometry assumes)
 BUDGETS = [
@@ -30,7 +32,7 @@ BUDGETS = [
     (r"^_ZN2pf8k_firstqILi8ELi3ELi1ELin?1ELb[01]ELb[01]EE", 0, 128, 4),
     # r2c split walk (c5, default since round 4: the next hi tile's rows loaded before the
     # stores): two 512-thread workgroups per CU, 128 VGPRs, no spill
-    (r"^_ZN2pf11k_r2c_walk1ILin?1ELb1ELb0ELi0ELi0EE", 0, 128, 4),
+    (WALK1, 0, 128, 4),
     # 12600 row kernel (c3, default since round 4: stages 4-5 fused over thread pairs,
     # HSFFT_ROW_F45=1, stage-5 twiddles from the transposed copy, HSFFT_ROW_TWN=4; the other
     # twiddle variants beside it): one 512-thread workgroup per CU
@@ -107,10 +109,11 @@ def test_hot_kernels_register_allocation():
 
 
 def test_no_wrong_result_probes_in_product():
-    """the timing probes that compute wrong results, and the variants measured slower that are
-    neither a default nor the independent schedule an every-word test compares against, exist
-    only in the development build (-DHSFFT_DEV_PROBES): the product library must not even
-    contain their names (knobs or kernels)"""
+    """the timing probes that computed wrong results, and the variants measured slower that were
+    neither a default nor the independent schedule an every-word test compares against, have
+    been removed with the development build that held them (-DHSFFT_DEV_PROBES; the figures are
+    in DESIGN.md §5): the library must not contain their names (knobs or kernels), so this
+    guards against their return"""
     if not os.path.exists(LIB):
         pytest.skip("lib/libhsfft.so not built")
     blob = open(LIB, "rb").read()
@@ -130,16 +133,19 @@ def test_no_wrong_result_probes_in_product():
         assert probe not in blob, probe
     names = _metadata()
     bad = [k for k in names
-           # timing probes: k_r2c_walk1<SGN, PFH, PFL, PROBE != 0>, k_row2<..., TWN = 2> (constant twiddles)
-           if re.match(r"^_ZN2pf11k_r2c_walk1ILin?1ELb[01]ELb[01]ELi[1-9]", k)
-           or re.match(r"^_ZN2mr6k_row2I.*ELi2EEEvNS_5MArgsE$", k)
-           # measured slower: walk1's other prefetch forms, the one-per-CU walk2, round 1's split
-           # kernel r8::k_r2c_last, the c3 row kernel's stage-5 twiddles through LDS (TWN = 3)
-           or (re.match(r"^_ZN2pf11k_r2c_walk1", k) and not re.match(r"^_ZN2pf11k_r2c_walk1ILin?1ELb1ELb0ELi0ELi0EE", k))
+           # timing probe: k_row2<..., TWN = 2> (constant twiddles)
+           if re.match(r"^_ZN2mr6k_row2I.*ELi2EEEvNS_5MArgsE$", k)
+           # k_r2c_walk1 has the sign as its only template parameter: any other instantiation
+           # (once: timing probes, other prefetch forms, the store token) is a variant come back
+           or (re.match(r"^_ZN2pf11k_r2c_walk1", k) and not re.match(WALK1, k))
+           # measured slower: the one-per-CU walk2, round 1's split kernel r8::k_r2c_last, the c3
+           # row kernel's stage-5 twiddles through LDS (TWN = 3)
            or re.match(r"^_ZN2pf11k_r2c_walk2", k)
            or re.match(r"^_ZN2r810k_r2c_last", k)
            or re.match(r"^_ZN2mr6k_row2I.*ELi3EEEvNS_5MArgsE$", k)]
     assert not bad, bad
+    walk1 = [k for k in names if k.startswith("_ZN2pf11k_r2c_walk1")]
+    assert len(walk1) == 2, walk1  # sign +1 and -1
 
 
 def _bx_lds_bytes():

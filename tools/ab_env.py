@@ -6,7 +6,7 @@ variant runs on the same input / output buffers, interleaved round by round; the
 its knobs per launch, so setting os.environ between calls switches the variant.
 
   python tools/ab_env.py --config c3 --var HSFFT_ROW_TWL --values 1,0 --rounds 6
-  python tools/ab_env.py --config c5 --values "unset" "HSFFT_R2C_WT=16;HSFFT_R2C_ORDER=0"
+  python tools/ab_env.py --config c5 --values "unset" "HSFFT_R2C_WT=16;HSFFT_PFP=4"
 
 A value is either one setting of --var ("unset" removes it) or a ';'-separated list of VAR=VAL
 assignments; every variable named anywhere is removed before a variant's own are applied.  The
