@@ -143,6 +143,49 @@ int hsfft_r2c_2d_full(fft_object p0, fft_real_object r1, const fft_type *d_in, f
  * Hermitian-consistent or not. */
 int hsfft_c2r_2d(fft_object p0, fft_real_object r1, const fft_data *d_in, fft_type *d_out, int batch);
 
+/* --- batched 2D convolution of real images ---------------------------------------------- */
+/* Sizes only, no device touched.  Each axis follows the 1D rule of fft_convolve / hsfft_convolve_batched
+ * on its own, with n and m the two operands' lengths on that axis: "linear" has clen = n + m - 1,
+ * "circular" clen = max(n, m); the padded transform size is P = next_power_of_two(clen).  Linear
+ * returns the window `type` selects -- "full" (or NULL): clen samples from 0; "same": max(n, m)
+ * samples from (clen - max(n, m)) / 2; "valid": max(n, m) - min(n, m) + 1 samples from
+ * min(n, m) - 1 -- and circular returns all P samples (type is still checked, then not used).
+ * Writes the output image's rows and columns and the padded sizes P0 = *pad_rows (from the row
+ * counts) and P1 = *pad_cols (from the widths); a NULL result pointer is skipped.  Returns 0, or
+ * HSFFT_ERR_ARG with a message for a NULL or unknown conv_type, an unknown type, a dimension
+ * < 1, P1 < 2 (both widths 1: a real plan of length 1 does not exist) or an empty window. */
+int hsfft_convolve_2d_shape(const char *type, const char *conv_type, int a_rows, int a_cols, int b_rows,
+                            int b_cols, int *out_rows, int *out_cols, int *pad_rows, int *pad_cols);
+/* d_a: batch contiguous row-major real images of a_rows x a_cols; d_b: b_batch images of b_rows x
+ * b_cols, where b_batch is batch (one kernel per image) or 1 (one kernel shared by every image, the
+ * filtering case); d_out: batch contiguous images of out_rows x out_cols (hsfft_convolve_2d_shape).
+ * The contract is compositional.  With w = P1/2+1, p0 = fft_init(P0, 1), q0 = fft_init(P0, -1), r1 =
+ * fft_real_init(P1, 1) and s1 = fft_real_init(P1, -1):
+ *   A = what hsfft_r2c_2d(p0, r1) gives on a placed at the top-left of a P0 x P1 image of +0.0,
+ *   B = the same for b,
+ *   C[k] = (A.re*B.re - A.im*B.im, A.re*B.im + A.im*B.re), every multiply, subtract and add rounded
+ *          on its own (the operand order of the reference's 1D product),
+ *   y = what hsfft_c2r_2d(q0, s1) gives on C,
+ *   out[r][c] = y[start0 + r][start1 + c] / (double)((long long)P0 * P1), one division per element.
+ * No zero row or column is skipped.  Internally the product runs on the transposed half spectra
+ * ([k1][k0]), so the last transpose of each forward transform and the first of the inverse are not
+ * run; padding, product and window use the row-copy and product kernels of the 1D convolution; the
+ * words are those of the composition above.  The four plans come from the library's convolution plan cache: a call
+ * with padded sizes it has seen before builds no plan.
+ * Asynchronous on the library stream under the device lock, like hsfft_exec_2d; the inputs are
+ * never written; Bluestein lengths would keep the error-word contract of hsfft_exec_batched
+ * (below), although power-of-two plans never take that path.  Returns 0 on success and for batch
+ * == 0.  HSFFT_ERR_ARG with a message -- before any device is touched -- for what
+ * hsfft_convolve_2d_shape rejects, NULL data pointers, batch < 0, b_batch not 1 or batch (when
+ * batch > 0), and a d_out byte range that overlaps either input's (each range with its own size).
+ * Scratch: the HSFFT_2D_CHUNK_MB buffer of the 2D transforms with the padded half spectrum as the
+ * image.  A call walks its batch in chunks of HSFFT_2D_CHUNK_MB / (3 x P0 x (P1/2+1) x 16) image
+ * pairs, at least one, halved while the allocation fails; a shared kernel's spectrum is one more
+ * image in the same buffer that the rule does not count.  No allocation per call. */
+int hsfft_convolve_2d_batched(const char *type, const char *conv_type, const fft_type *d_a, int a_rows,
+                              int a_cols, const fft_type *d_b, int b_rows, int b_cols, int b_batch,
+                              fft_type *d_out, int batch);
+
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */
 int hsfft_fill_complex(fft_data *d_x, int64_t count, uint64_t seed, uint64_t offset);
@@ -174,7 +217,6 @@ int hsfft_bench_copy(const void *d_src, void *d_dst, size_t bytes, int iters, fl
  * milliseconds in *ms): batch transposed half spectra d_in[b][k1][k0] ((n1/2+1) x n0) to the full
  * layout d_out[b][k0][k1] (n0 x n1), mirror half included.  n1 even, batch >= 1. */
 int hsfft_bench_transpose_herm(const fft_data *d_in, fft_data *d_out, int n0, int n1, int batch, int iters, float *ms);
-
 /* Bluestein M = 2^18 (e.g. N = 99991) runs as one persistent launch whose workgroups must all
  * be resident at once; the library checks that with the occupancy API before launching, and a
  * grid that cannot be co-resident runs on the three-launch path at once (same results, more

@@ -204,8 +204,11 @@ static int transpose_herm(const void *in, void *out, long long n0, long long n1,
  * most the batch and at most what keeps a chunk's row count an int; halved while the allocation
  * fails; the last chunk may be ragged.  hsfft_exec_2d needs one copy of the chunk and
  * hsfft_exec_columns two; for the real 2D transforms the image is the half spectrum, n0 x
- * (n1/2+1) elements: hsfft_r2c_2d and hsfft_r2c_2d_full need one copy, hsfft_c2r_2d two. */
-static void *chunk_scratch(long long img_elems, int max_dim, int copies, int batch, long long *per_chunk)
+ * (n1/2+1) elements: hsfft_r2c_2d and hsfft_r2c_2d_full need one copy, hsfft_c2r_2d two.
+ * `extra_elems` more elements are allocated behind the chunk copies without counting towards the
+ * rule (the 2D convolution's shared kernel spectrum, hsfft_conv2d.h). */
+static void *chunk_scratch(long long img_elems, int max_dim, int copies, int batch, long long *per_chunk,
+                           long long extra_elems = 0)
 {
     const size_t img_bytes = sizeof(fft_data) * (size_t)img_elems;
     long long ci = (long long)(hs_env_mb("HSFFT_2D_CHUNK_MB", 1024.0) / ((size_t)copies * img_bytes));
@@ -214,7 +217,7 @@ static void *chunk_scratch(long long img_elems, int max_dim, int copies, int bat
     if (ci < 1) ci = 1;
     void *S;
     for (;;) {
-        S = hs_scratch(HS_SCR_2D, (size_t)copies * img_bytes * (size_t)ci);
+        S = hs_scratch(HS_SCR_2D, (size_t)copies * img_bytes * (size_t)ci + sizeof(fft_data) * (size_t)extra_elems);
         if (S || ci == 1) break;
         ci = (ci + 1) / 2;
     }

@@ -34,32 +34,47 @@ int find_optimal_fft_length(int min_length, const char *conv_type, int length1, 
 
 /* Plan cache: entries are reference counted -- a slot in use by any thread is never
  * evicted; when every slot is busy the call builds a private pair and frees it afterwards.
- * A slot being built carries its P and mode with `building` set: a concurrent request for the
- * same length waits for that build instead of evicting another slot for a duplicate pair. */
-#define HS_CONV_CACHE 8
+ * A slot being built carries its P, mode and kind with `building` set: a concurrent request for
+ * the same key waits for that build instead of evicting another slot for a duplicate pair.
+ * Two kinds of pair share the slots: the real plans fft_real_init(P, +-1) of the 1D and 2D
+ * convolutions (kind 0) and the c2c plans fft_init(P, +-1) of the 2D convolution's columns
+ * (kind 1). */
+#define HS_CONV_CACHE 16
 static pthread_mutex_t g_clock = PTHREAD_MUTEX_INITIALIZER;
 static pthread_cond_t g_cbuilt = PTHREAD_COND_INITIALIZER;
 static struct {
-    int P, mode, refs, building;
+    int P, mode, kind, refs, building;
     unsigned long long used; /* LRU stamp */
-    fft_real_object f, i;
+    void *f, *i;
 } g_cache[HS_CONV_CACHE];
 static unsigned long long g_cache_clock;
 
-typedef struct {
-    fft_real_object f, i;
-    int slot; /* cache slot held, or -1 for a private pair */
-} conv_pair;
+static void *pair_init(int kind, int P, int sgn)
+{
+    return kind ? (void *)fft_init(P, sgn) : (void *)fft_real_init(P, sgn);
+}
 
-static conv_pair conv_plans(int P)
+static void pair_free(int kind, void *f, void *i)
+{
+    if (kind) {
+        free_fft(f);
+        free_fft(i);
+    } else {
+        free_real_fft(f);
+        free_real_fft(i);
+    }
+}
+
+/* the forward and inverse plan of length P of the given kind into *f, *i (NULL where a build
+ * failed); returns the cache slot held, or -1 for a private pair */
+static int pair_get(int kind, int P, void **f, void **i)
 {
     const int mode = hsfft_get_twiddle_mode();
-    conv_pair cp = {NULL, NULL, -1};
     pthread_mutex_lock(&g_clock);
     for (;;) {
         int victim = -1, pending = 0;
         for (int k = 0; k < HS_CONV_CACHE; k++) {
-            const int same = g_cache[k].P == P && g_cache[k].mode == mode;
+            const int same = g_cache[k].P == P && g_cache[k].mode == mode && g_cache[k].kind == kind;
             if (same && g_cache[k].building) {
                 pending = 1;
                 break;
@@ -67,85 +82,108 @@ static conv_pair conv_plans(int P)
             if (same && g_cache[k].f) {
                 g_cache[k].refs++;
                 g_cache[k].used = ++g_cache_clock;
-                cp.f = g_cache[k].f;
-                cp.i = g_cache[k].i;
-                cp.slot = k;
+                *f = g_cache[k].f;
+                *i = g_cache[k].i;
                 pthread_mutex_unlock(&g_clock);
-                return cp;
+                return k;
             }
             if (g_cache[k].refs == 0 && !g_cache[k].building &&
                 (victim < 0 || !g_cache[k].f || (g_cache[victim].f && g_cache[k].used < g_cache[victim].used)))
                 victim = k;
         }
-        if (pending) { /* another thread is building this length: wait, then look again */
+        if (pending) { /* another thread is building this pair: wait, then look again */
             pthread_cond_wait(&g_cbuilt, &g_clock);
             continue;
         }
         if (victim < 0) break;
         /* reserve the least recently used idle slot; build and free outside the lock (plans
          * of other lengths / devices are not held up) */
-        fft_real_object of = g_cache[victim].f, oi = g_cache[victim].i;
+        void *of = g_cache[victim].f, *oi = g_cache[victim].i;
+        const int okind = g_cache[victim].kind;
         g_cache[victim].P = P;
         g_cache[victim].mode = mode;
+        g_cache[victim].kind = kind;
         g_cache[victim].refs = 1;
         g_cache[victim].building = 1;
         g_cache[victim].used = ++g_cache_clock;
         g_cache[victim].f = g_cache[victim].i = NULL;
         pthread_mutex_unlock(&g_clock);
-        if (of) {
-            free_real_fft(of);
-            free_real_fft(oi);
-        }
-        cp.f = fft_real_init(P, 1);
-        cp.i = fft_real_init(P, -1);
-        cp.slot = victim;
+        if (of) pair_free(okind, of, oi);
+        *f = pair_init(kind, P, 1);
+        *i = pair_init(kind, P, -1);
+        int slot = victim;
         pthread_mutex_lock(&g_clock);
         g_cache[victim].building = 0;
-        if (cp.f && cp.i) {
-            g_cache[victim].f = cp.f;
-            g_cache[victim].i = cp.i;
+        if (*f && *i) {
+            g_cache[victim].f = *f;
+            g_cache[victim].i = *i;
         } else { /* failed build: the slot goes back empty, the caller keeps what it got */
             g_cache[victim].P = 0;
             g_cache[victim].refs = 0;
-            cp.slot = -1;
+            slot = -1;
         }
         pthread_cond_broadcast(&g_cbuilt);
         pthread_mutex_unlock(&g_clock);
-        return cp;
+        return slot;
     }
     pthread_mutex_unlock(&g_clock);
-    cp.f = fft_real_init(P, 1);
-    cp.i = fft_real_init(P, -1);
-    return cp;
+    *f = pair_init(kind, P, 1);
+    *i = pair_init(kind, P, -1);
+    return -1;
 }
 
-static void conv_plans_done(conv_pair cp)
+static void pair_put(int kind, int slot, void *f, void *i)
 {
-    if (cp.slot < 0) {
-        free_real_fft(cp.f);
-        free_real_fft(cp.i);
+    if (slot < 0) {
+        pair_free(kind, f, i);
         return;
     }
     pthread_mutex_lock(&g_clock);
-    g_cache[cp.slot].refs--;
+    g_cache[slot].refs--;
     pthread_mutex_unlock(&g_clock);
 }
+
+hs_conv_pair hs_conv_plans(int P)
+{
+    void *f = NULL, *i = NULL;
+    hs_conv_pair cp;
+    cp.slot = pair_get(0, P, &f, &i);
+    cp.f = f;
+    cp.i = i;
+    return cp;
+}
+
+void hs_conv_plans_done(hs_conv_pair cp) { pair_put(0, cp.slot, cp.f, cp.i); }
+
+hs_conv_cpair hs_conv_cplans(int P)
+{
+    void *f = NULL, *i = NULL;
+    hs_conv_cpair cp;
+    cp.slot = pair_get(1, P, &f, &i);
+    cp.f = f;
+    cp.i = i;
+    return cp;
+}
+
+void hs_conv_cplans_done(hs_conv_cpair cp) { pair_put(1, cp.slot, cp.f, cp.i); }
 
 /* (hsfft_finalize) free every idle cached plan pair; slots in use or being built are kept */
 void hs_conv_cache_release(void)
 {
-    fft_real_object fr[2 * HS_CONV_CACHE];
-    int n = 0;
+    void *fr[2 * HS_CONV_CACHE];
+    int kind[HS_CONV_CACHE], n = 0;
     pthread_mutex_lock(&g_clock);
     for (int k = 0; k < HS_CONV_CACHE; k++)
         if (g_cache[k].refs == 0 && !g_cache[k].building && g_cache[k].f) {
-            fr[n++] = g_cache[k].f;
-            fr[n++] = g_cache[k].i;
+            kind[n] = g_cache[k].kind;
+            fr[2 * n] = g_cache[k].f;
+            fr[2 * n + 1] = g_cache[k].i;
+            n++;
             g_cache[k].f = g_cache[k].i = NULL;
             g_cache[k].P = 0;
         }
     pthread_mutex_unlock(&g_clock);
-    for (int k = 0; k < n; k++) free_real_fft(fr[k]);
+    for (int k = 0; k < n; k++) pair_free(kind[k], fr[2 * k], fr[2 * k + 1]);
 }
 
 /* output window of the reference (convolve.c:163-201); returns length or -1 */
@@ -185,10 +223,33 @@ static int conv_setup(const char *conv_type, int n, int m, int *linear, int *cle
     return 0;
 }
 
+/* one axis of the 2D convolution (hsfft_conv2d.h): the padded length into *P, the window's first
+ * sample into *start; returns the window's length, or -1 with the message set.  The rule is the
+ * 1D call's (conv_setup / conv_window); `type` is checked for circular too, where it is not used */
+int hs_conv_axis(const char *type, const char *conv_type, int n, int m, int *P, int *start)
+{
+    int linear, clen;
+    if (n < 1 || m < 1 || (long long)n + m - 1 > (1LL << 30)) {
+        hs_seterr("2D convolution: axis lengths %d and %d are out of range", n, m);
+        return -1;
+    }
+    if (type && strcmp(type, "full") && strcmp(type, "same") && strcmp(type, "valid")) {
+        hs_seterr("2D convolution: output type '%s' is not 'full', 'same' or 'valid'", type);
+        return -1;
+    }
+    if (conv_type == NULL || (strcmp(conv_type, "linear") && strcmp(conv_type, "circular"))) {
+        hs_seterr("2D convolution: convolution type '%s' is not 'linear' or 'circular'",
+                  conv_type ? conv_type : "(null)");
+        return -1;
+    }
+    if (conv_setup(conv_type, n, m, &linear, &clen, P)) return -1;
+    return conv_window(type, linear, clen, *P, n, m, start);
+}
+
 /* device core: a (rows of n), b (rows of m) -> res (rows of P; divided by P if scale) */
 static int conv_device(int P, const double *d_a, int n, const double *d_b, int m, double *d_res, int batch, int scale)
 {
-    const conv_pair cp = conv_plans(P);
+    const hs_conv_pair cp = hs_conv_plans(P);
     fft_real_object f = cp.f, iv = cp.i;
     /* the reference multiplies all P mirrored bins (convolve.c:147-151), but its c2r reads
      * bins 0..P/2 only (real.c:169-179): compact spectra of P/2+1 bins give the same bits
@@ -197,7 +258,7 @@ static int conv_device(int P, const double *d_a, int n, const double *d_b, int m
     double *pa = hs_scratch(HS_SCR_CONV_PAD, sizeof(double) * (size_t)P * 2 * (size_t)batch);
     fft_data *spec = hs_scratch(HS_SCR_CONV_SPEC, sizeof(fft_data) * (size_t)cd * 2 * (size_t)batch);
     if (!pa || !spec) {
-        conv_plans_done(cp);
+        hs_conv_plans_done(cp);
         hs_seterr("convolution scratch allocation failed (%d rows of P = %d)", batch, P);
         return HSFFT_ERR_NOMEM;
     }
@@ -210,7 +271,7 @@ static int conv_device(int P, const double *d_a, int n, const double *d_b, int m
     if (!rc) rc = hs_c2r_rows(iv, A, B, cd, d_res, batch); /* product fused into the pre-twiddle */
     if (!rc && scale) rc = hsd_scale_real(d_res, P, batch, P, (double)P) ? HSFFT_ERR_DEVICE : 0;
     if (!rc) rc = hsd_sync() ? HSFFT_ERR_DEVICE : 0;
-    conv_plans_done(cp);
+    hs_conv_plans_done(cp);
     return rc;
 }
 

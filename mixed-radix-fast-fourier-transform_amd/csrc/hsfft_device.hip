@@ -1537,3 +1537,4 @@ int hsd_pass_timer_read(int n, float *ms)
 }  // extern "C"
 
 #include "hsfft_2d.h"
+#include "hsfft_conv2d.h"

@@ -139,6 +139,26 @@ void hs_sync_call(int enter);
 /* release this layer's device objects (hsfft_finalize): idle convolution plan pairs, real
  * plans' device twiddles on the current device */
 void hs_conv_cache_release(void);
+/* Cached plan pairs of the convolutions (hsfft_convolve.c), keyed by length and twiddle mode and
+ * reference counted: the forward and inverse real plans of a padded length, and the forward and
+ * inverse c2c plans of the 2D convolution's padded row count.  Every get is paired with its done;
+ * slot < 0 marks a private pair (every slot busy) that done frees; f or i is NULL where a build
+ * failed.  A repeated request for a cached length builds nothing. */
+typedef struct {
+    fft_real_object f, i;
+    int slot;
+} hs_conv_pair;
+typedef struct {
+    fft_object f, i;
+    int slot;
+} hs_conv_cpair;
+hs_conv_pair hs_conv_plans(int P);
+void hs_conv_plans_done(hs_conv_pair cp);
+hs_conv_cpair hs_conv_cplans(int P);
+void hs_conv_cplans_done(hs_conv_cpair cp);
+/* one axis of the 2D convolution by the 1D rule: padded length, window start; returns the
+ * window length or -1 (message set) */
+int hs_conv_axis(const char *type, const char *conv_type, int n, int m, int *P, int *start);
 void hs_real_release_device(int dev);
 /* bytes from an environment knob given in MiB (default dflt_mb; at least 1 MiB) */
 size_t hs_env_mb(const char *name, double dflt_mb);

@@ -66,6 +66,9 @@ SIGNATURES = {
     "hsfft_r2c_2d": (CI, [VP, VP, VP, VP, CI]),
     "hsfft_r2c_2d_full": (CI, [VP, VP, VP, VP, CI]),
     "hsfft_c2r_2d": (CI, [VP, VP, VP, VP, CI]),
+    "hsfft_convolve_2d_shape": (CI, [ctypes.c_char_p, ctypes.c_char_p, CI, CI, CI, CI, ctypes.POINTER(CI),
+                                     ctypes.POINTER(CI), ctypes.POINTER(CI), ctypes.POINTER(CI)]),
+    "hsfft_convolve_2d_batched": (CI, [ctypes.c_char_p, ctypes.c_char_p, VP, CI, CI, VP, CI, CI, CI, VP, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -363,6 +366,78 @@ def irfft2(X, n1, sgn=-1):
     if X.size == 0:
         return np.empty(shape, dtype=np.float64)
     return _real_2d(c2r_2d, X, X.shape[-2], n1, sgn, np.float64, shape)
+
+
+def _name(s):
+    return s.encode() if isinstance(s, str) else s
+
+
+def convolve_2d_shape(mode, boundary, a_rows, a_cols, b_rows, b_cols):
+    """(out_rows, out_cols, pad_rows, pad_cols) of hsfft_convolve_2d_batched: sizes only, no device touched"""
+    v = [CI(0) for _ in range(4)]
+    check(lib().hsfft_convolve_2d_shape(_name(mode), _name(boundary), a_rows, a_cols, b_rows, b_cols,
+                                        *(ctypes.byref(x) for x in v)), "convolve_2d_shape")
+    return tuple(x.value for x in v)
+
+
+def convolve_2d_batched(mode, boundary, d_a, a_rows, a_cols, d_b, b_rows, b_cols, b_batch, d_out, batch):
+    """batch real images a_rows x a_cols convolved with b_batch (batch or 1) images b_rows x b_cols
+    into batch images of the size convolve_2d_shape gives; mode full | same | valid, boundary
+    linear | circular"""
+    return check(lib().hsfft_convolve_2d_batched(_name(mode), _name(boundary), VP(d_a.ptr), a_rows, a_cols, VP(d_b.ptr),
+                                                 b_rows, b_cols, b_batch, VP(d_out.ptr), batch), "convolve_2d_batched")
+
+
+_CONV_MODES, _CONV_BOUNDARIES = ("full", "same", "valid"), ("linear", "circular")
+
+
+def _conv_axis(mode, boundary, n, m):
+    """window length of one axis by the library's rule (hsfft_convolve_2d_shape), for shape checks
+    that must not load the library"""
+    if boundary == "circular":
+        return 1 << (max(n, m) - 1).bit_length()
+    return {"full": n + m - 1, "same": max(n, m), "valid": max(n, m) - min(n, m) + 1}[mode]
+
+
+def convolve2d(a, b, mode="full", boundary="linear"):
+    """2D convolution over the last two axes of float64 arrays: a of shape (..., rows, cols), b with
+    the same leading shape or a single 2D kernel shared by every image; uploads, runs
+    hsfft_convolve_2d_batched and downloads.  The output size follows the library's per-axis rule:
+    full / same / valid windows for boundary="linear", the whole power-of-two padded image for
+    "circular"."""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    if mode not in _CONV_MODES or boundary not in _CONV_BOUNDARIES:
+        raise ValueError(f"convolve2d: mode is one of {_CONV_MODES}, boundary one of {_CONV_BOUNDARIES}")
+    if a.ndim < 2 or b.ndim < 2:
+        raise ValueError("convolve2d needs arrays of at least two dimensions")
+    if b.ndim != 2 and b.shape[:-2] != a.shape[:-2]:
+        raise ValueError("convolve2d: b is one 2D kernel or has a's leading shape")
+    (ar, ac), (br, bc) = a.shape[-2:], b.shape[-2:]
+    if min(ar, ac, br, bc) < 1:
+        raise ValueError("convolve2d: empty image")
+    if ac == 1 and bc == 1:
+        raise ValueError("convolve2d: both widths are 1 (no real transform of length 1)")
+    shape = a.shape[:-2] + (_conv_axis(mode, boundary, ar, br), _conv_axis(mode, boundary, ac, bc))
+    if a.size == 0:
+        return np.empty(shape, dtype=np.float64)
+    batch = a.size // (ar * ac)
+    b_batch = batch if b.ndim != 2 else 1
+    if tuple(shape[-2:]) != convolve_2d_shape(mode, boundary, ar, ac, br, bc)[:2]:
+        raise HsfftError("convolve2d: the library's output shape differs from the binding's")
+    made = []
+    try:
+        d_a = DeviceBuffer.from_array(a)
+        made.append(d_a.free)
+        d_b = DeviceBuffer.from_array(b)
+        made.append(d_b.free)
+        d_out = DeviceBuffer(int(np.prod(shape)) * 8)
+        made.append(d_out.free)
+        convolve_2d_batched(mode, boundary, d_a, ar, ac, d_b, br, bc, b_batch, d_out, batch)
+        synchronize()
+        return d_out.to_array(np.float64).reshape(shape)
+    finally:
+        for release in reversed(made):
+            release()
 
 
 def r2c_batched(rplan, d_in, d_out, batch):
