@@ -42,8 +42,8 @@ int hsfft_synchronize(void);
  * otherwise persists for the process: up to the largest chunk a call needed (c2c chains
  * HSFFT_CHUNK_MB, default 256 MiB x 2; Bluestein HSFFT_BLUE_CHUNK_MB, 4 GiB x 2; real paths
  * HSFFT_REAL_CHUNK_MB, 16 GiB; the 2D paths, complex and real, HSFFT_2D_CHUNK_MB, 1 GiB -- the
- * real 2D transforms hold that and the real paths' buffer together -- each halved while
- * allocation fails). */
+ * real 2D transforms hold that and the real paths' buffer together; the overlap-add filter
+ * HSFFT_FILTER_CHUNK_MB, 1 GiB -- each halved while allocation fails). */
 int hsfft_release_scratch(void);
 /* Teardown: waits for every device's work, then releases every device object the library
  * holds on every device -- scratch pool, page-locked staging slots, the device state of every
@@ -185,6 +185,56 @@ int hsfft_convolve_2d_shape(const char *type, const char *conv_type, int a_rows,
 int hsfft_convolve_2d_batched(const char *type, const char *conv_type, const fft_type *d_a, int a_rows,
                               int a_cols, const fft_type *d_b, int b_rows, int b_cols, int b_batch,
                               fft_type *d_out, int batch);
+
+/* --- batched overlap-add filtering of long real rows by one shared kernel ---------------- */
+/* Linear convolution of `batch` rows of n reals with ONE kernel of m reals, by overlap-add: each
+ * row is cut into blocks of L samples, each block is convolved with the kernel at the padded
+ * length P = L + m - 1, and the m - 1 samples by which neighbouring blocks overlap are added.  The
+ * kernel is transformed once per call, the transforms have P points instead of
+ * next_power_of_two(n + m - 1), and the scratch is bounded by a knob, not by the job. */
+#define HSFFT_FILTER_BLOCK_MIN 8192 /* floor of the automatic block: the fastest measured block */
+/* Sizes only, no device touched; a NULL result pointer is skipped.  clen = n + m - 1.  The window
+ * is the 1D rule of fft_convolve / hsfft_convolve_batched: "full" (or NULL): clen samples from 0;
+ * "same": max(n, m) samples from (clen - max(n, m)) / 2; "valid": max(n, m) - min(n, m) + 1
+ * samples from min(n, m) - 1; its length goes to *out_len.  With Q = max(2,
+ * next_power_of_two(clen)): block == 0 is automatic, P = min(max(HSFFT_FILTER_BLOCK_MIN,
+ * next_power_of_two(4 m)), Q); otherwise P = block, which must be a power of two, >= 2 and >= m.
+ * L = P - m + 1 and nseg = ceil(n / L) blocks per row.  With nseg > 1, L >= m - 1 is required, so
+ * that at most two blocks meet at any output sample (the automatic rule always satisfies it).
+ * Returns 0, or HSFFT_ERR_ARG with a message for n or m < 1, clen > 2^30, an unknown type, or a
+ * block that breaks these rules. */
+int hsfft_filter_shape(const char *type, int n, int m, int block, int *out_len, int *P, int *L, int *nseg);
+/* d_x: batch contiguous rows of n reals; d_h: one kernel of m reals, shared by every row; d_out:
+ * batch contiguous rows of out_len reals (hsfft_filter_shape).  The contract is compositional.
+ * With f = fft_real_init(P, 1), g = fft_real_init(P, -1), for block s of row b:
+ *   u_s = x[b][sL .. sL+L) at the start of P words of +0.0 (the last block is shorter; nothing is
+ *         read past the end of row b),
+ *   H   = bins 0..P/2 of the reference's fft_r2c_exec(f) on h at the start of P words of +0.0,
+ *   U_s = the same transform of u_s,
+ *   C_s[k] = (U.re*H.re - U.im*H.im, U.re*H.im + U.im*H.re), every operation rounded on its own,
+ *          the block's spectrum as the left operand (the reference's 1D product),
+ *   y_s = the reference's fft_c2r_exec(g) of C_s,  v_s[i] = y_s[i] / (double)P, one division each,
+ *   full[g] for g = sL + j, 0 <= j < L, s < nseg:  v_s[j] when s == 0 or j >= m - 1, else
+ *          v_s[j] + v_{s-1}[L + j], in this order;
+ *   full[g] for g >= nseg L (the tail after the last block) = v_{nseg-1}[g - (nseg-1) L],
+ *   out[b][t] = full[start + t].
+ * v_s is, word for word, what the reference's fft_convolve("full", "linear", u_s[0..L), L, h, m, .)
+ * returns, so the output is a sum of reference results; with P == Q there is one block and the
+ * words are those of hsfft_convolve_batched on the same rows with the kernel replicated per row.
+ * No block is skipped for being zero.  Where two blocks add and both terms are NaN, the payload is
+ * not part of the contract; everything else is.
+ * Asynchronous on the library stream under the device lock, like hsfft_exec_2d; the inputs are
+ * never written; every output word is written exactly once and none is read.  Returns 0 on success
+ * and for batch == 0.  HSFFT_ERR_ARG with a message -- before any device is touched -- for NULL
+ * pointers, batch < 0, what hsfft_filter_shape rejects, and a d_out byte range that overlaps
+ * d_x's or d_h's.  The two real plans come from the convolution plan cache.
+ * Scratch: two pool buffers, no allocation per call.  Blocks are numbered q = b nseg + s and walked
+ * in chunks of HSFFT_FILTER_CHUNK_MB / (P x 8 + (P/2+1) x 16) consecutive blocks
+ * (HSFFT_FILTER_CHUNK_MB: default 1024 MiB, at least 1, read per call), at least one, halved while
+ * the allocation fails; a chunk may cross row boundaries.  The kernel's spectrum and the m - 1
+ * words a chunk hands to the next lie behind the second buffer, and the rule does not count them. */
+int hsfft_filter_batched(const char *type, const fft_type *d_x, int n, const fft_type *d_h, int m, int block,
+                         fft_type *d_out, int batch);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */

@@ -99,6 +99,9 @@ int hs_r2c_rows(fft_real_object r, const fft_type *d_in, fft_data *d_out, int ba
 /* c2r of rows xdist complex apart (hsfft_real.c); d_b != NULL: of the product d_a .* d_b */
 int hs_c2r_rows(fft_real_object r, const fft_data *d_a, const fft_data *d_b, long long xdist, fft_type *d_out,
                 int batch);
+/* the device copy of r's twiddle2 table (N/2 complex) on the current device, uploaded on first use
+ * and kept until free_real_fft / hsfft_finalize; NULL on failure (hsfft_real.c) */
+void *hs_real_tw2_device(fft_real_object r);
 /* Scratch buffers, one per class and device, grown on demand and used under the device lock.
  * Two names with one number share a buffer: their users are separate public entry points that
  * hold the device lock for their whole call, wait for the device before they return, and never
@@ -106,7 +109,10 @@ int hs_c2r_rows(fft_real_object r, const fft_data *d_a, const fft_data *d_b, lon
 enum {
     HS_SCR_CHAIN0 = 0,    /* intermediates of a pass chain, alternating */
     HS_SCR_CHAIN1 = 1,
-    HS_SCR_SPARE = 2,     /* unused (kept: the pool's size is unchanged) */
+    HS_SCR_FILTER = 2,    /* hsfft_filter_batched (hsfft_filter.h): a chunk's gathered blocks.  A class of
+                           * its own, and its spectra in HS_SCR_CONV_SPEC, whose other user runs on the
+                           * library stream too: the call is asynchronous, so it shares no buffer with
+                           * an entry point that writes its scratch from another stream */
     HS_SCR_BLUE_MID = 3,  /* Bluestein M-point intermediate, or the persistent launch's images */
     HS_SCR_REAL_Z = 4,    /* real transforms: the inner c2c's N/2-point rows */
     HS_SCR_STAGE_IN = 5,  /* drop-in fft_exec / fft_r2c_exec / fft_c2r_exec: staged input */

@@ -51,7 +51,7 @@ fft_real_object fft_real_init(int N, int sgn)
     return r;
 }
 
-static void *tw2_device(fft_real_object r)
+void *hs_real_tw2_device(fft_real_object r)
 {
     const int d = hsd_get_device();
     if (d < 0 || d >= HS_MAX_DEV) return NULL;
@@ -140,7 +140,7 @@ static fft_data *real_chunk(int h, int batch, long long *chunk)
 int hs_r2c_rows(fft_real_object r, const fft_type *d_in, fft_data *d_out, int batch, int compact)
 {
     hs_entry *e = hs_entry_get(r->cobj);
-    void *tw2 = e ? tw2_device(r) : NULL;
+    void *tw2 = e ? hs_real_tw2_device(r) : NULL;
     const int h = r->cobj->N, N = 2 * h;
     const long long xdist = compact ? h + 1 : N;
     long long chunk = 1;
@@ -167,7 +167,7 @@ int hs_c2r_rows(fft_real_object r, const fft_data *d_a, const fft_data *d_b, lon
                 int batch)
 {
     hs_entry *e = hs_entry_get(r->cobj);
-    void *tw2 = e ? tw2_device(r) : NULL;
+    void *tw2 = e ? hs_real_tw2_device(r) : NULL;
     const int h = r->cobj->N, N = 2 * h;
     long long chunk = 1;
     fft_data *Zi = tw2 ? real_chunk(h, batch, &chunk) : NULL;

@@ -69,6 +69,9 @@ SIGNATURES = {
     "hsfft_convolve_2d_shape": (CI, [ctypes.c_char_p, ctypes.c_char_p, CI, CI, CI, CI, ctypes.POINTER(CI),
                                      ctypes.POINTER(CI), ctypes.POINTER(CI), ctypes.POINTER(CI)]),
     "hsfft_convolve_2d_batched": (CI, [ctypes.c_char_p, ctypes.c_char_p, VP, CI, CI, VP, CI, CI, CI, VP, CI]),
+    "hsfft_filter_shape": (CI, [ctypes.c_char_p, CI, CI, CI, ctypes.POINTER(CI), ctypes.POINTER(CI), ctypes.POINTER(CI),
+                                ctypes.POINTER(CI)]),
+    "hsfft_filter_batched": (CI, [ctypes.c_char_p, VP, CI, VP, CI, CI, VP, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -433,6 +436,56 @@ def convolve2d(a, b, mode="full", boundary="linear"):
         d_out = DeviceBuffer(int(np.prod(shape)) * 8)
         made.append(d_out.free)
         convolve_2d_batched(mode, boundary, d_a, ar, ac, d_b, br, bc, b_batch, d_out, batch)
+        synchronize()
+        return d_out.to_array(np.float64).reshape(shape)
+    finally:
+        for release in reversed(made):
+            release()
+
+
+def filter_shape(mode, n, m, block=0):
+    """(out_len, P, L, nseg) of hsfft_filter_batched: sizes only, no device touched; block 0 is automatic"""
+    v = [CI(0) for _ in range(4)]
+    check(lib().hsfft_filter_shape(_name(mode), n, m, block, *(ctypes.byref(x) for x in v)), "filter_shape")
+    return tuple(x.value for x in v)
+
+
+def filter_batched(mode, d_x, n, d_h, m, block, d_out, batch):
+    """batch real rows of n samples filtered by one kernel of m taps, by overlap-add with blocks
+    padded to `block` (0: automatic), into batch rows of the length filter_shape gives; mode
+    full | same | valid"""
+    return check(lib().hsfft_filter_batched(_name(mode), VP(d_x.ptr), n, VP(d_h.ptr), m, block, VP(d_out.ptr), batch),
+                 "filter_batched")
+
+
+def oaconvolve(x, h, mode="full", block=0):
+    """linear convolution of the float64 rows x, of shape (n,) or (batch, n), with one 1-D kernel h
+    by overlap-add: uploads, runs hsfft_filter_batched and downloads"""
+    x, h = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(h, dtype=np.float64)
+    if mode not in _CONV_MODES:
+        raise ValueError(f"oaconvolve: mode is one of {_CONV_MODES}")
+    if x.ndim not in (1, 2) or h.ndim != 1:
+        raise ValueError("oaconvolve needs x of one or two dimensions and a one-dimensional kernel")
+    n, m = x.shape[-1], h.shape[0]
+    if n < 1 or m < 1:
+        raise ValueError("oaconvolve: empty row or kernel")
+    if block < 0 or (block and (block & (block - 1) or block < 2 or block < m)):
+        raise ValueError("oaconvolve: block is 0 or a power of two >= 2 and >= the kernel length")
+    shape = x.shape[:-1] + (_conv_axis(mode, "linear", n, m),)
+    if x.size == 0:
+        return np.empty(shape, dtype=np.float64)
+    batch = x.size // n
+    if shape[-1] != filter_shape(mode, n, m, block)[0]:
+        raise HsfftError("oaconvolve: the library's output length differs from the binding's")
+    made = []
+    try:
+        d_x = DeviceBuffer.from_array(x)
+        made.append(d_x.free)
+        d_h = DeviceBuffer.from_array(h)
+        made.append(d_h.free)
+        d_out = DeviceBuffer(int(np.prod(shape)) * 8)
+        made.append(d_out.free)
+        filter_batched(mode, d_x, n, d_h, m, block, d_out, batch)
         synchronize()
         return d_out.to_array(np.float64).reshape(shape)
     finally:
