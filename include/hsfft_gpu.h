@@ -43,7 +43,8 @@ int hsfft_synchronize(void);
  * HSFFT_CHUNK_MB, default 256 MiB x 2; Bluestein HSFFT_BLUE_CHUNK_MB, 4 GiB x 2; real paths
  * HSFFT_REAL_CHUNK_MB, 16 GiB; the 2D paths, complex and real, HSFFT_2D_CHUNK_MB, 1 GiB -- the
  * real 2D transforms hold that and the real paths' buffer together; the overlap-add filter
- * HSFFT_FILTER_CHUNK_MB, 1 GiB -- each halved while allocation fails). */
+ * HSFFT_FILTER_CHUNK_MB, 1 GiB; the STFT and its inverse HSFFT_STFT_CHUNK_MB, 1 GiB, in the
+ * filter's first buffer -- each halved while allocation fails). */
 int hsfft_release_scratch(void);
 /* Teardown: waits for every device's work, then releases every device object the library
  * holds on every device -- scratch pool, page-locked staging slots, the device state of every
@@ -235,6 +236,72 @@ int hsfft_filter_shape(const char *type, int n, int m, int block, int *out_len, 
  * words a chunk hands to the next lie behind the second buffer, and the rule does not count them. */
 int hsfft_filter_batched(const char *type, const fft_type *d_x, int n, const fft_type *d_h, int m, int block,
                          fft_type *d_out, int batch);
+
+/* --- batched short-time Fourier transform of real rows, and its inverse ------------------ */
+/* The frames of an STFT overlap: they start `hop` samples apart and are N long, each is multiplied
+ * by a window of N reals and transformed by r2c.  The inverse runs c2r on every frame, windows it
+ * again and adds the frames that cover each output sample.  Both compose the unchanged row
+ * transforms with one new kernel each; the window and the framing are not fused into a transform
+ * pass. */
+/* Sizes only, no device touched; a NULL result pointer is skipped and a rejected call writes
+ * nothing.  N is the frame length (even, >= 2; N = 2 * r->cobj->N for a real plan r), hop >= 1,
+ * n >= 1 the row length, center 0 or 1.  *lpad = center ? N/2 : 0 and *bins = N/2 + 1.  Frame f
+ * covers the positions p = f hop - lpad + j, 0 <= j < N, of its row; a position outside [0, n)
+ * reads as +0.0.  center == 0 requires n >= N and gives *nframes = 1 + (n - N) / hop (trailing
+ * samples that no frame reaches are not read); center == 1 gives *nframes = 1 + n / hop, the
+ * frame count of the usual centred STFT, with zero instead of reflected padding.  Returns 0, or
+ * HSFFT_ERR_ARG with a message for an odd N, N < 2, hop < 1, n < 1, a center other than 0 or 1,
+ * n < N with center == 0, or n or N > 2^30. */
+int hsfft_stft_shape(int n, int N, int hop, int center, int *nframes, int *bins, int *lpad);
+/* d_x: batch contiguous rows of n reals; d_w: a window of N = 2 * r->cobj->N reals shared by every
+ * frame, or NULL; d_out: batch x nframes x (N/2+1) complex, contiguous, frame-major.  The contract
+ * is compositional.  For frame f of row b:
+ *   u[j] = xpad[f hop - lpad + j] * w[j], one multiply rounded on its own, computed for every j: a
+ *          padded position contributes +0.0 * w[j], whatever that is (-0.0 for a negative tap);
+ *          with d_w == NULL there is no multiply, u[j] = xpad[f hop - lpad + j];
+ *   out[b][f][0..N/2] = bins 0..N/2 of the reference's fft_r2c_exec(r) on u -- the words
+ *          hsfft_r2c_batched_compact writes.
+ * r is applied as planned: either sign, any even length a real plan supports (mixed-radix or
+ * Bluestein inner lengths, N == 2); Bluestein inner lengths keep the error-word contract of
+ * hsfft_exec_batched (below).  Nothing is read outside row b, and no frame is skipped for being
+ * zero.
+ * Asynchronous on the library stream under the device lock, like hsfft_filter_batched; the inputs
+ * are never written; every output word is written exactly once and none is read.  Returns 0 on
+ * success and for batch == 0.  HSFFT_ERR_ARG with a message -- before any device is touched -- for
+ * a NULL plan, d_x or d_out, batch < 0, what hsfft_stft_shape rejects, nframes x batch > 2^31 - 1,
+ * n x batch or nframes x batch x N > 2^40 (the byte counts of the call's buffers then fit 64 bits
+ * with room to spare), and a d_out byte range that overlaps d_x's or d_w's.
+ * Scratch: one pool buffer, no allocation per call.  Frames are numbered q = b nframes + f and
+ * walked in chunks of HSFFT_STFT_CHUNK_MB / (N x 8) consecutive frames (HSFFT_STFT_CHUNK_MB:
+ * default 1024 MiB, at least 1, read per call), at least one, halved while the allocation fails; a
+ * chunk may cross row boundaries.  Per chunk the frames are gathered and windowed into the scratch
+ * and transformed from there straight into d_out. */
+int hsfft_stft_batched(fft_real_object r, const fft_type *d_x, int n, const fft_type *d_w, int hop,
+                       int center, fft_data *d_out, int batch);
+/* d_spec: batch x nframes x (N/2+1) complex with N = 2 * ri->cobj->N; d_w: a window of N reals or
+ * NULL; d_out: batch contiguous rows of n reals.  The contract is compositional and holds for any
+ * input words, Hermitian-consistent or not:
+ *   y_f = the reference's fft_c2r_exec(ri) on frame f (it reads bins 0..N/2, here at pitch N/2+1),
+ *   v_f[j] = y_f[j] / (double)N, one division,
+ *   t_f[j] = v_f[j] * w[j], one multiply; v_f[j] itself with d_w == NULL.
+ * For output sample i of row b let F(i) be the frames f in [0, nframes) with 0 <= i + lpad - f hop
+ * < N, in increasing f.  acc starts as the first frame's term t_f[i + lpad - f hop], not as 0.0,
+ * and each later term is added in that order, one rounded add each.  With normalize != 0, env is
+ * built the same way from w[j] * w[j], each product rounded (from 1.0 per frame with d_w == NULL),
+ * and out[b][i] = acc / env, one division; no threshold is applied, a zero envelope gives the IEEE
+ * result.  With normalize == 0, out[b][i] = acc.  A sample that no frame covers (hop > N, or
+ * beyond the last frame's reach) is +0.0 in both modes.  n >= 1 is otherwise free: it need not be
+ * the length the frames came from, and a shorter n trims.  Where two or more NaN terms meet, the
+ * payload is not part of the contract; everything else is.
+ * Conventions and rejections as for hsfft_stft_batched, with hop >= 1, center 0 or 1, 1 <= n <=
+ * 2^30 (n < N is allowed here), nframes >= 1, the same bounds on the totals, and a d_out range
+ * that overlaps d_spec's or d_w's.
+ * Scratch: the same pool buffer.  Whole rows are walked in chunks of HSFFT_STFT_CHUNK_MB /
+ * (nframes x N x 8) rows, at least one, halved while the allocation fails down to one row, then
+ * HSFFT_ERR_NOMEM; a row's frames never straddle a chunk.  One row larger than the knob still runs
+ * as one chunk. */
+int hsfft_istft_batched(fft_real_object ri, const fft_data *d_spec, int nframes, const fft_type *d_w,
+                        int hop, int center, int normalize, fft_type *d_out, int n, int batch);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */

@@ -475,7 +475,8 @@ int hsfft_finalize(void)
 /* Chunk sizes, one knob per path, all read per call: HSFFT_CHUNK_MB (c2c intermediates of
  * 3+-pass chains), HSFFT_BLUE_CHUNK_MB (Bluestein M-point intermediates), HSFFT_REAL_CHUNK_MB
  * (the real paths' inner intermediate, hsfft_real.c), HSFFT_HOST_CHUNK_MB (the host pipeline's
- * staging slots), HSFFT_2D_CHUNK_MB (the 2D and column paths' scratch, hsfft_2d.h). */
+ * staging slots), HSFFT_2D_CHUNK_MB (the 2D and column paths' scratch, hsfft_2d.h),
+ * HSFFT_FILTER_CHUNK_MB (hsfft_filter.h), HSFFT_STFT_CHUNK_MB (hsfft_stft.h). */
 size_t hs_env_mb(const char *name, double dflt_mb)
 {
     const char *s = getenv(name);

@@ -113,6 +113,11 @@ enum {
                            * its own, and its spectra in HS_SCR_CONV_SPEC, whose other user runs on the
                            * library stream too: the call is asynchronous, so it shares no buffer with
                            * an entry point that writes its scratch from another stream */
+    HS_SCR_STFT = 2,      /* hsfft_stft_batched / hsfft_istft_batched (hsfft_stft.h): a chunk's windowed frames,
+                           * or its frames after the c2r.  The filter's number under a second name although
+                           * these calls are asynchronous too: all three run wholly on the library stream
+                           * under the device lock and never call each other, so stream order keeps one
+                           * call's kernels behind the previous call's, whichever of the three it was */
     HS_SCR_BLUE_MID = 3,  /* Bluestein M-point intermediate, or the persistent launch's images */
     HS_SCR_REAL_Z = 4,    /* real transforms: the inner c2c's N/2-point rows */
     HS_SCR_STAGE_IN = 5,  /* drop-in fft_exec / fft_r2c_exec / fft_c2r_exec: staged input */

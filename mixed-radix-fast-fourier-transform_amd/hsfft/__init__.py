@@ -72,6 +72,9 @@ SIGNATURES = {
     "hsfft_filter_shape": (CI, [ctypes.c_char_p, CI, CI, CI, ctypes.POINTER(CI), ctypes.POINTER(CI), ctypes.POINTER(CI),
                                 ctypes.POINTER(CI)]),
     "hsfft_filter_batched": (CI, [ctypes.c_char_p, VP, CI, VP, CI, CI, VP, CI]),
+    "hsfft_stft_shape": (CI, [CI, CI, CI, CI, ctypes.POINTER(CI), ctypes.POINTER(CI), ctypes.POINTER(CI)]),
+    "hsfft_stft_batched": (CI, [VP, VP, CI, VP, CI, CI, VP, CI]),
+    "hsfft_istft_batched": (CI, [VP, VP, CI, VP, CI, CI, CI, VP, CI, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -491,6 +494,115 @@ def oaconvolve(x, h, mode="full", block=0):
     finally:
         for release in reversed(made):
             release()
+
+
+def stft_shape(n, n_fft, hop, center=False):
+    """(nframes, bins, lpad) of hsfft_stft_batched: sizes only, no device touched"""
+    v = [CI(0) for _ in range(3)]
+    check(lib().hsfft_stft_shape(n, n_fft, hop, int(center), *(ctypes.byref(x) for x in v)), "stft_shape")
+    return tuple(x.value for x in v)
+
+
+def _opt_ptr(d):
+    return VP(d.ptr) if d is not None else None
+
+
+def stft_batched(rplan, d_x, n, d_w, hop, center, d_out, batch):
+    """batch real rows of n samples -> batch x nframes x (rplan.n/2+1) complex: frames of rplan.n
+    samples `hop` apart, times the window d_w (None: no window), through the r2c of rplan"""
+    return check(lib().hsfft_stft_batched(rplan.ptr, VP(d_x.ptr), n, _opt_ptr(d_w), hop, int(center), VP(d_out.ptr), batch),
+                 "stft_batched")
+
+
+def istft_batched(rplan, d_spec, nframes, d_w, hop, center, normalize, d_out, n, batch):
+    """batch x nframes x (rplan.n/2+1) complex -> batch real rows of n samples: c2r of rplan on
+    every frame, / rplan.n, times the window, overlap-added; normalize divides by the summed
+    squared window"""
+    return check(lib().hsfft_istft_batched(rplan.ptr, VP(d_spec.ptr), nframes, _opt_ptr(d_w), hop, int(center),
+                                           int(normalize), VP(d_out.ptr), n, batch), "istft_batched")
+
+
+def _stft_window(who, window, n_fft):
+    if window is None:
+        return None
+    window = np.ascontiguousarray(window, dtype=np.float64)
+    if window.shape != (n_fft,):
+        raise ValueError(f"{who}: the window is one-dimensional, n_fft = {n_fft} long")
+    return window
+
+
+def _stft_run(call, plan_args, x, window, out_dtype, out_shape):
+    """plan, upload x and the window, run call(plan, d_x, d_w, d_out), download"""
+    made = []
+    try:
+        rp = RealPlan(*plan_args)
+        made.append(rp.close)
+        d_x = DeviceBuffer.from_array(x)
+        made.append(d_x.free)
+        d_w = None
+        if window is not None:
+            d_w = DeviceBuffer.from_array(window)
+            made.append(d_w.free)
+        d_out = DeviceBuffer(int(np.prod(out_shape)) * np.dtype(out_dtype).itemsize)
+        made.append(d_out.free)
+        call(rp, d_x, d_w, d_out)
+        synchronize()
+        return d_out.to_array(out_dtype).reshape(out_shape)
+    finally:
+        for release in reversed(made):
+            release()
+
+
+def stft(x, n_fft, hop, window=None, center=False):
+    """short-time Fourier transform of the float64 rows x, of shape (n,) or (batch, n): complex128
+    (batch, nframes, n_fft/2+1), without the batch axis for 1-D input; frames of n_fft samples `hop`
+    apart times `window`, forward r2c, unscaled.  center=True puts sample f*hop in the middle of
+    frame f, with zeros outside the row.  Plans, uploads, runs hsfft_stft_batched and downloads"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    center = bool(center)
+    if x.ndim not in (1, 2):
+        raise ValueError("stft needs x of one or two dimensions")
+    if n_fft < 2 or n_fft % 2 or hop < 1:
+        raise ValueError("stft: n_fft is even and >= 2, hop >= 1")
+    n = x.shape[-1]
+    if n < 1 or (not center and n < n_fft):
+        raise ValueError("stft: a row is empty or, without center, shorter than n_fft")
+    window = _stft_window("stft", window, n_fft)
+    nframes = 1 + n // hop if center else 1 + (n - n_fft) // hop
+    shape = x.shape[:-1] + (nframes, n_fft // 2 + 1)
+    if x.size == 0:
+        return np.empty(shape, dtype=np.complex128)
+    batch = x.size // n
+    if nframes != stft_shape(n, n_fft, hop, center)[0]:
+        raise HsfftError("stft: the library's frame count differs from the binding's")
+    return _stft_run(lambda rp, d_x, d_w, d_out: stft_batched(rp, d_x, n, d_w, hop, center, d_out, batch),
+                     (n_fft, 1), x, window, np.complex128, shape)
+
+
+def istft(S, hop, window=None, center=False, normalize=True, length=None):
+    """inverse of stft for complex128 S of shape (nframes, bins) or (batch, nframes, bins), n_fft =
+    2 (bins - 1): float64 rows of `length` samples (None: (nframes-1)*hop + n_fft - 2*lpad, what
+    the frames cover of the row); normalize divides by the overlap-added squared window.  Plans,
+    uploads, runs hsfft_istft_batched and downloads"""
+    S = np.ascontiguousarray(S, dtype=np.complex128)
+    center = bool(center)
+    if S.ndim not in (2, 3):
+        raise ValueError("istft needs S of two or three dimensions")
+    nframes, bins = S.shape[-2:]
+    if nframes < 1 or bins < 2 or hop < 1:
+        raise ValueError("istft: at least one frame, at least two bins, hop >= 1")
+    n_fft = 2 * (bins - 1)
+    window = _stft_window("istft", window, n_fft)
+    n = (nframes - 1) * hop + n_fft - (n_fft if center else 0) if length is None else length
+    if n < 1:
+        raise ValueError("istft: the output length is below 1")
+    shape = S.shape[:-2] + (n,)
+    if S.size == 0:
+        return np.empty(shape, dtype=np.float64)
+    batch = S.size // (nframes * bins)
+    return _stft_run(lambda rp, d_s, d_w, d_out: istft_batched(rp, d_s, nframes, d_w, hop, center, normalize, d_out, n,
+                                                               batch),
+                     (n_fft, -1), S, window, np.float64, shape)
 
 
 def r2c_batched(rplan, d_in, d_out, batch):
