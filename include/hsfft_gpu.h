@@ -44,12 +44,14 @@ int hsfft_synchronize(void);
  * HSFFT_REAL_CHUNK_MB, 16 GiB; the 2D paths, complex and real, HSFFT_2D_CHUNK_MB, 1 GiB -- the
  * real 2D transforms hold that and the real paths' buffer together; the overlap-add filter
  * HSFFT_FILTER_CHUNK_MB, 1 GiB; the STFT and its inverse HSFFT_STFT_CHUNK_MB, 1 GiB, in the
- * filter's first buffer -- each halved while allocation fails). */
+ * filter's first buffer; the cosine and sine transforms HSFFT_DCT_CHUNK_MB, 1 GiB, in the
+ * filter's two buffers -- each halved while allocation fails).  Also frees the current device's
+ * cached DCT rotation tables (at most four, rebuilt on demand). */
 int hsfft_release_scratch(void);
 /* Teardown: waits for every device's work, then releases every device object the library
  * holds on every device -- scratch pool, page-locked staging slots, the device state of every
  * live plan (twiddles, odd-radix constants, Bluestein chirp / hk), real plans' device twiddles,
- * idle convolution plans, persistent-launch counters and the calling thread's error words (a
+ * the cached DCT rotation tables, idle convolution plans, persistent-launch counters and the calling thread's error words (a
  * pending launch error of the calling thread is reported as by hsfft_synchronize), timing and
  * ordering events, the library streams.  Plans stay valid and everything is re-created on
  * demand, so the library remains usable.  Call it before process exit (bench.py and the test
@@ -302,6 +304,60 @@ int hsfft_stft_batched(fft_real_object r, const fft_type *d_x, int n, const fft_
  * as one chunk. */
 int hsfft_istft_batched(fft_real_object ri, const fft_data *d_spec, int nframes, const fft_type *d_w,
                         int hop, int center, int normalize, fft_type *d_out, int n, int batch);
+
+/* --- batched cosine and sine transforms (DCT-II / III, DST-II / III) of real rows --------- */
+/* The conventions are scipy's with norm=None, unnormalised, for rows of N = n reals:
+ *   DCT-II   X[k] = 2 sum_n x[n] cos(pi k (2n+1) / 2N)
+ *   DCT-III  y[n] = X[0] + 2 sum_{k>=1} X[k] cos(pi k (2n+1) / 2N)
+ *   DST-II   X[k] = 2 sum_n x[n] sin(pi (k+1) (2n+1) / 2N)
+ *   DST-III  y[n] = (-1)^n X[N-1] + 2 sum_{k<N-1} X[k] sin(pi (k+1) (2n+1) / 2N)
+ * so that type 3 of type 2 of x is 2N x.  Each is Makhoul's N-point algorithm: the unchanged r2c
+ * or c2r row transform of length N with one new kernel before it and one after; the permutation
+ * and the rotation are not fused into a transform pass.  Only even n: a real plan needs an even
+ * length.  Odd lengths, types I and IV and orthonormal scaling are out of scope. */
+#define HSFFT_KIND_COS 0
+#define HSFFT_KIND_SIN 1
+/* Host only, no device touched: the n/2+1 rotation words the calls below use, h_tw[k] = (c_k, s_k)
+ * for 0 <= k <= n/2 from one libm sincos(PI2 * (double)k / (4.0 * (double)n), &s_k, &c_k) each (PI2
+ * of highspeedFFT.h; the angle is pi k / 2n).  Returns 0, or HSFFT_ERR_ARG with a message for n
+ * odd, n < 2, n > 2^30 or a NULL h_tw. */
+int hsfft_dct_twiddles(int n, fft_data *h_tw);
+/* kind: HSFFT_KIND_COS / HSFFT_KIND_SIN; type: 2 or 3; d_in, d_out: batch contiguous rows of n
+ * reals.  The contract is compositional and bit-exact.  With N = n, h = N/2, f = fft_real_init(N, 1),
+ * g = fft_real_init(N, -1) and t = the table of hsfft_dct_twiddles(N), per row:
+ * DCT-II:
+ *   v[j] = x[2j], v[N-1-j] = x[2j+1] for j < h,
+ *   V = bins 0..h of the reference's fft_r2c_exec(f) on v -- the words hsfft_r2c_batched_compact
+ *       writes,
+ *   re_k = V.re*c_k + V.im*s_k, im_k = V.im*c_k - V.re*s_k, every multiply, add and subtract rounded
+ *       on its own and computed for every k with no special case,
+ *   out[k] = 2.0*re_k for 0 <= k <= h, out[N-k] = -2.0*im_k for 1 <= k < h.
+ * DCT-III:
+ *   V[0] = (X[0], +0.0) with no arithmetic (an infinite X[0] stays infinite),
+ *   V[k] = (a*c_k + b*s_k, a*s_k - b*c_k) with a = X[k], b = X[N-k] for 1 <= k <= h, each operation
+ *       rounded on its own,
+ *   y = the reference's fft_c2r_exec(g) on V (it reads bins 0..h, here at pitch h+1), unscaled,
+ *   out[2j] = y[j], out[2j+1] = y[N-1-j] for j < h.
+ * DST-II is DCT-II of x' with x'[n] = x[n] for even n and the sign bit of x[n] flipped for odd n
+ * (of zeros and NaNs too), written reversed: out[k] = X'[N-1-k].  DST-III is DCT-III of X'[k] =
+ * X[N-1-k] with out[n] = y[n] for even n and the sign bit flipped for odd n.  Both are index and
+ * sign variants inside the same two kernels, with no extra pass over memory.  Where two NaN terms
+ * meet in one add, the payload is not part of the contract; everything else is.
+ * The two plans come from the convolution plan cache: they follow the calling thread's twiddle
+ * mode, and a repeated length builds nothing.  Any even length a real plan supports (mixed-radix
+ * or Bluestein inner lengths, N == 2); Bluestein inner lengths keep the error-word contract of
+ * hsfft_exec_batched (below).
+ * Asynchronous on the library stream under the device lock, like hsfft_stft_batched; the input is
+ * never written; every output word is written exactly once and none is read.  Returns 0 on
+ * success and for batch == 0.  HSFFT_ERR_ARG with a message -- before any device is touched -- for
+ * a kind other than 0 or 1, a type other than 2 or 3, n odd, n < 2 or n > 2^30, batch < 0,
+ * n x batch > 2^40, NULL pointers, d_in == d_out or input and output byte ranges that overlap.
+ * Scratch: two pool buffers (the filter's), no allocation per call.  Rows are walked in chunks of
+ * HSFFT_DCT_CHUNK_MB / (N x 8 + (N/2+1) x 16) rows (HSFFT_DCT_CHUNK_MB: default 1024 MiB, at least
+ * 1, read per call), at least one, halved while the allocation fails.  The table is cached on the
+ * device, four lengths per device, the least recently used one replaced: a length not in the cache
+ * builds its table on the host and uploads it synchronously. */
+int hsfft_dct_batched(int kind, int type, const fft_type *d_in, fft_type *d_out, int n, int batch);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */

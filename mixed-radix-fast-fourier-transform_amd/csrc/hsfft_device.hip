@@ -1540,3 +1540,4 @@ int hsd_pass_timer_read(int n, float *ms)
 #include "hsfft_conv2d.h"
 #include "hsfft_filter.h"
 #include "hsfft_stft.h"
+#include "hsfft_dct.h"

@@ -118,6 +118,10 @@ enum {
                            * these calls are asynchronous too: all three run wholly on the library stream
                            * under the device lock and never call each other, so stream order keeps one
                            * call's kernels behind the previous call's, whichever of the three it was */
+    HS_SCR_DCT = 2,       /* hsfft_dct_batched (hsfft_dct.h): a chunk's permuted rows, or its rows after the
+                           * c2r.  A third name for the same number by the same argument: the call is
+                           * asynchronous, runs wholly on the library stream under the device lock and
+                           * calls neither the filter nor the STFT, so stream order separates the users */
     HS_SCR_BLUE_MID = 3,  /* Bluestein M-point intermediate, or the persistent launch's images */
     HS_SCR_REAL_Z = 4,    /* real transforms: the inner c2c's N/2-point rows */
     HS_SCR_STAGE_IN = 5,  /* drop-in fft_exec / fft_r2c_exec / fft_c2r_exec: staged input */
@@ -129,6 +133,9 @@ enum {
     HS_SCR_BLUE_MID2 = 8, /* Bluestein second intermediate (fused middle kernel) */
     HS_SCR_HOST_OUT = 9,  /* hsfft_exec_batched_host: two download slots */
     HS_SCR_CONV_SPEC = 10,/* convolution: both compact spectra */
+    HS_SCR_DCT_SPEC = 10, /* hsfft_dct_batched: a chunk's compact spectra, as the filter keeps its own in
+                           * HS_SCR_CONV_SPEC; the convolution, the filter and this call all run on the
+                           * library stream under the device lock and never call each other */
     HS_SCR_2D = 11,       /* hsfft_exec_2d / hsfft_exec_columns / the 2D real transforms (hsfft_2d.h): the
                            * chunk between the row transforms and the transposes; a class of its own,
                            * because the row transforms in between use the chain, Bluestein and
@@ -171,6 +178,15 @@ void hs_conv_cplans_done(hs_conv_cpair cp);
  * window length or -1 (message set) */
 int hs_conv_axis(const char *type, const char *conv_type, int n, int m, int *P, int *start);
 void hs_real_release_device(int dev);
+/* The cosine and sine transforms' rotation table (hsfft_dct.c), n/2+1 words (cos, sin)(pi k / 2n).
+ * hs_dct_table (device lock of `dev` held, `dev` current): its copy on the device from a cache of
+ * four lengths per device, the least recently used one replaced; a miss builds the table on the
+ * host and uploads it synchronously; NULL with the message set on failure.  hs_dct_release_device
+ * (the same lock held, the device's work waited for): frees the device's cached tables; they are
+ * rebuilt on demand. */
+#define HS_DCT_MAX_LEN (1 << 30)
+const void *hs_dct_table(int dev, int n);
+void hs_dct_release_device(int dev);
 /* bytes from an environment knob given in MiB (default dflt_mb; at least 1 MiB) */
 size_t hs_env_mb(const char *name, double dflt_mb);
 

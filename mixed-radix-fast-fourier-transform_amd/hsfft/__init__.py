@@ -75,6 +75,8 @@ SIGNATURES = {
     "hsfft_stft_shape": (CI, [CI, CI, CI, CI, ctypes.POINTER(CI), ctypes.POINTER(CI), ctypes.POINTER(CI)]),
     "hsfft_stft_batched": (CI, [VP, VP, CI, VP, CI, CI, VP, CI]),
     "hsfft_istft_batched": (CI, [VP, VP, CI, VP, CI, CI, CI, VP, CI, CI]),
+    "hsfft_dct_twiddles": (CI, [CI, VP]),
+    "hsfft_dct_batched": (CI, [CI, CI, VP, VP, CI, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -603,6 +605,71 @@ def istft(S, hop, window=None, center=False, normalize=True, length=None):
     return _stft_run(lambda rp, d_s, d_w, d_out: istft_batched(rp, d_s, nframes, d_w, hop, center, normalize, d_out, n,
                                                                batch),
                      (n_fft, -1), S, window, np.float64, shape)
+
+
+KIND_COS, KIND_SIN = 0, 1  # include/hsfft_gpu.h
+
+
+def dct_twiddles(n):
+    """the n/2+1 rotation words (cos, sin)(pi k / 2n) of hsfft_dct_batched as complex128: host only"""
+    t = np.empty(max(int(n), 0) // 2 + 1, dtype=np.complex128)
+    check(lib().hsfft_dct_twiddles(n, _ptr(t)), "dct_twiddles")
+    return t
+
+
+def dct_batched(kind, type, d_in, d_out, n, batch):
+    """batch real rows of n samples -> batch rows of n: kind KIND_COS / KIND_SIN, type 2 or 3,
+    scipy's conventions with norm=None"""
+    return check(lib().hsfft_dct_batched(kind, type, VP(d_in.ptr), VP(d_out.ptr), n, batch), "dct_batched")
+
+
+def _dct_run(who, kind, type, x, inverse):
+    """check the shape, upload x, run hsfft_dct_batched and download; inverse: the other type, then
+    one division by 2.0 * n per word"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if type not in (2, 3):
+        raise ValueError(f"{who}: type is 2 or 3")
+    if x.ndim not in (1, 2):
+        raise ValueError(f"{who} needs x of one or two dimensions")
+    n = x.shape[-1]
+    if n < 2 or n % 2:
+        raise ValueError(f"{who}: the row length is even and >= 2")
+    if x.size == 0:
+        return np.empty(x.shape, dtype=np.float64)
+    made = []
+    try:
+        d_in = DeviceBuffer.from_array(x)
+        made.append(d_in.free)
+        d_out = DeviceBuffer(x.nbytes)
+        made.append(d_out.free)
+        dct_batched(kind, 5 - type if inverse else type, d_in, d_out, n, x.size // n)
+        synchronize()
+        y = d_out.to_array(np.float64).reshape(x.shape)
+    finally:
+        for release in reversed(made):
+            release()
+    return y / (2.0 * n) if inverse else y
+
+
+def dct(x, type=2):
+    """DCT-II or DCT-III (scipy.fft.dct, norm=None) of the float64 rows x, of shape (n,) or
+    (batch, n), n even: uploads, runs hsfft_dct_batched and downloads"""
+    return _dct_run("dct", KIND_COS, type, x, False)
+
+
+def dst(x, type=2):
+    """DST-II or DST-III (scipy.fft.dst, norm=None) of the float64 rows x, of shape (n,) or (batch, n)"""
+    return _dct_run("dst", KIND_SIN, type, x, False)
+
+
+def idct(x, type=2):
+    """inverse of dct(., type): the other type, divided by 2.0 * n in numpy (scipy.fft.idct, norm=None)"""
+    return _dct_run("idct", KIND_COS, type, x, True)
+
+
+def idst(x, type=2):
+    """inverse of dst(., type): the other type, divided by 2.0 * n in numpy (scipy.fft.idst, norm=None)"""
+    return _dct_run("idst", KIND_SIN, type, x, True)
 
 
 def r2c_batched(rplan, d_in, d_out, batch):
