@@ -42,7 +42,8 @@ int hsfft_synchronize(void);
  * otherwise persists for the process: up to the largest chunk a call needed (c2c chains
  * HSFFT_CHUNK_MB, default 256 MiB x 2; Bluestein HSFFT_BLUE_CHUNK_MB, 4 GiB x 2; real paths
  * HSFFT_REAL_CHUNK_MB, 16 GiB; the 2D paths, complex and real, HSFFT_2D_CHUNK_MB, 1 GiB -- the
- * real 2D transforms hold that and the real paths' buffer together; the overlap-add filter
+ * real 2D transforms hold that and the real paths' buffer together, the 2D cosine and sine
+ * transforms that and the two buffers of HSFFT_DCT_CHUNK_MB; the overlap-add filter
  * HSFFT_FILTER_CHUNK_MB, 1 GiB; the STFT and its inverse HSFFT_STFT_CHUNK_MB, 1 GiB, in the
  * filter's first buffer; the cosine and sine transforms HSFFT_DCT_CHUNK_MB, 1 GiB, in the
  * filter's two buffers -- each halved while allocation fails).  Also frees the current device's
@@ -97,7 +98,7 @@ int hsfft_convolve_batched(const char *type, const char *conv_type, const fft_ty
                            int batch);
 
 /* --- transforms along other axes: transpose, 2D, columns -------------------------------- */
-/* All three are asynchronous on the library stream and run under the device lock, like
+/* All of these are asynchronous on the library stream and run under the device lock, like
  * hsfft_exec_batched; Bluestein lengths keep that call's error-word contract (below).  They
  * return HSFFT_ERR_ARG -- before any device is touched -- for NULL pointers, d_in == d_out or
  * input and output ranges that overlap, a negative batch or a dimension < 1; batch == 0 returns
@@ -110,6 +111,11 @@ int hsfft_convolve_batched(const char *type, const char *conv_type, const fft_ty
 /* out[b][c][r] = in[b][r][c]; d_in != d_out, ranges must not overlap.  A pure copy of 16-byte
  * elements: every word, NaN payloads included, arrives unchanged. */
 int hsfft_transpose_batched(const fft_data *d_in, fft_data *d_out, int rows, int cols, int batch);
+/* The same transpose for batch matrices of rows x cols doubles, with the same contract and the same
+ * rejections (the byte ranges are rows x cols x batch x 8 long): a pure copy of 8-byte elements,
+ * every word -- NaN payloads, signed zeros, subnormals -- arrives unchanged.  The buffers need the
+ * alignment of a double only.  The transpose between the row transforms of hsfft_dct_2d_batched. */
+int hsfft_transpose_real_batched(const fft_type *d_in, fft_type *d_out, int rows, int cols, int batch);
 /* 2D c2c of batch row-major images of p0->N rows by p1->N columns: the 1D transform of p1 on every
  * row, then the 1D transform of p0 on every column of that result (this order is part of the
  * contract: results are bit-identical to the reference's fft_exec applied that way). No scaling.
@@ -358,6 +364,34 @@ int hsfft_dct_twiddles(int n, fft_data *h_tw);
  * device, four lengths per device, the least recently used one replaced: a length not in the cache
  * builds its table on the host and uploads it synchronously. */
 int hsfft_dct_batched(int kind, int type, const fft_type *d_in, fft_type *d_out, int n, int batch);
+
+/* --- batched 2D cosine and sine transforms of real images -------------------------------- */
+/* batch contiguous row-major real images of n0 rows by n1 columns -> batch images of the same
+ * shape.  kind1 (HSFFT_KIND_COS / HSFFT_KIND_SIN) is the transform along the rows (axis 1), kind0
+ * the transform along the columns (axis 0); one type, 2 or 3, for both axes, in the conventions
+ * above (scipy's dctn / dstn with norm=None for equal kinds; mixed kinds are what a Poisson solver
+ * with mixed boundaries needs).  Type 3 of type 2 of x is 4 n0 n1 x.
+ * The contract is compositional and bit-exact: the result is, word for word, hsfft_dct_batched(kind1,
+ * type) on every row and then hsfft_dct_batched(kind0, type) on every column of that result -- rows
+ * first, then columns, for both types.  The row transforms are that call's kernels unchanged; in
+ * between the images are transposed by the copy of hsfft_transpose_real_batched.  Per chunk: rows
+ * d_in -> scratch, transpose scratch -> d_out, rows d_out -> scratch (the columns, now contiguous),
+ * transpose scratch -> d_out; four trips through HBM beside the row transforms' own.
+ * Everything else is hsfft_dct_batched's: both plan pairs come from the convolution plan cache and
+ * both rotation tables from the four-entry cache (the two lengths alternate inside one call and
+ * both stay cached), Bluestein inner lengths keep the error-word contract of hsfft_exec_batched,
+ * the call is asynchronous on the library stream under the device lock, d_in is never written and
+ * every output word is written.  Returns 0 on success and for batch == 0.  HSFFT_ERR_ARG with a
+ * message -- before any device is touched -- for a kind other than 0 or 1, a type other than 2 or
+ * 3, n0 or n1 odd, below 2 or above 2^30, batch < 0, n0 x n1 x batch > 2^40, NULL pointers,
+ * d_in == d_out or input and output byte ranges that overlap.
+ * Scratch: one copy of a chunk in the 2D transforms' pool buffer, beside the two buffers the row
+ * transforms keep (and walk in chunks of their own, HSFFT_DCT_CHUNK_MB).  A call walks its batch in
+ * chunks of HSFFT_2D_CHUNK_MB / (n0 x n1 x 8) images (default 1024 MiB), at least one, at most the
+ * batch and at most what keeps a chunk's row count -- images x max(n0, n1) -- an int; halved while
+ * the allocation fails; the last chunk may be ragged. */
+int hsfft_dct_2d_batched(int kind0, int kind1, int type, const fft_type *d_in, fft_type *d_out, int n0, int n1,
+                         int batch);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */

@@ -12,6 +12,10 @@
  * the same way from hs_r2c_rows() / hs_c2r_rows(), hs_c2c_rows() over the n1/2+1 columns of the
  * half spectrum and the transposes; the full layout's mirror half is written by the one kernel
  * they add, k_transpose_herm.
+ *
+ * k_transpose8 is the same transpose for 8-byte elements (hsfft_transpose_real_batched); the 2D
+ * cosine and sine transforms of hsfft_dct2d.h run it between the row transforms of hsfft_dct.h
+ * (DESIGN.md §14).
  */
 #include "hsfft_gpu.h"
 #include "hsfft_host.h"
@@ -113,6 +117,82 @@ static int transpose(const void *in, void *out, long long rows, long long cols, 
     return rc ? HSFFT_ERR_DEVICE : 0;
 }
 
+/* out[b][c][r] = in[b][r][c] for 8-byte elements (hsfft_transpose_real_batched and the 2D cosine and
+ * sine transforms, hsfft_dct2d.h): one TS x TS tile of doubles per workgroup of 256 threads, the
+ * skeleton of k_transpose.
+ *
+ * Both global sides are 8 B per lane -- caller buffers need the alignment of a double only -- with
+ * lanes on consecutive elements of the side's fastest axis: at TS = 64 a wave-instruction covers
+ * one 512-B run.  The tile is staged through LDS with a row pitch of TS + 1 doubles = 130 dwords.
+ * The row-wise stores (ds_write_b64, banks modulo 32 dwords, groups of 16 contiguous lanes) cover
+ * 128 contiguous bytes = 32 consecutive dwords per group: conflict-free at any pitch.  The
+ * column-wise loads (ds_read_b64, banks modulo 64 dwords = 32 slots of 8 B, the two 32-lane halves
+ * as groups) put lane l at dword 130 l + const, that is at slot (65 l + const) mod 32 = (l + const)
+ * mod 32, and a half holds 32 distinct l mod 32: conflict-free.  At pitch TS every lane of a half
+ * would sit on one slot (32-way).  Every LDS address is a multiple of 8 bytes.
+ *
+ * The batch is flattened into the 1D grid as in k_transpose, 64-bit arithmetic throughout, edge
+ * guards on both sides.  No arithmetic on the data: plain 8-B loads and stores, every word -- NaN
+ * payloads, signed zeros, subnormals -- copied verbatim. */
+template <int TS>
+__global__ __launch_bounds__(256) void k_transpose8(const double *__restrict__ in, double *__restrict__ out,
+                                                    long long rows, long long cols, long long ntr, long long ntc,
+                                                    long long tile0)
+{
+    constexpr int P = TS + 1, RY = 256 / TS, NK = TS / RY;
+    __shared__ double tile[TS * P];
+    const long long t = tile0 + blockIdx.x, per = ntr * ntc;
+    const long long b = t / per, rem = t - b * per;
+    const long long tr = rem / ntc, tc = rem - tr * ntc;
+    const int tx = threadIdx.x % TS, ty = threadIdx.x / TS;
+    const long long r0 = tr * TS, c0 = tc * TS;
+    const double *src = in + b * rows * cols;
+    double *dst = out + b * rows * cols;
+    double v[NK];
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long r = r0 + ty + k * RY, c = c0 + tx;
+        if (r < rows && c < cols) v[k] = src[r * cols + c];
+    }
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long r = r0 + ty + k * RY, c = c0 + tx;
+        if (r < rows && c < cols) tile[(ty + k * RY) * P + tx] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        const long long c = c0 + ty + k * RY, r = r0 + tx; /* output row c, output column r */
+        if (c < cols && r < rows) dst[c * rows + r] = tile[tx * P + ty + k * RY];
+    }
+}
+
+/* (device lock held by the caller) queue the 8-byte transposes of `batch` matrices on the selected
+ * stream; the tile is 64 x 65 x 8 = 33280 bytes of static LDS */
+static int launch8(const double *in, double *out, long long rows, long long cols, long long batch)
+{
+    constexpr int ts = 64;
+    const long long ntr = (rows + ts - 1) / ts, ntc = (cols + ts - 1) / ts;
+    if (ntr > MAX_GRID / ntc) {
+        snprintf(g_err, sizeof g_err, "transpose: %lld x %lld tiles per matrix", ntr, ntc);
+        return -1;
+    }
+    const long long total = batch * ntr * ntc;
+    for (long long t0 = 0; t0 < total; t0 += MAX_GRID) {
+        const long long g = total - t0 < MAX_GRID ? total - t0 : MAX_GRID;
+        hipLaunchKernelGGL(k_transpose8<ts>, dim3((unsigned)g), dim3(256), 0, stream(), in, out, rows, cols, ntr, ntc, t0);
+        HCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+static int transpose8(const double *in, double *out, long long rows, long long cols, long long batch)
+{
+    const int rc = launch8(in, out, rows, cols, batch);
+    if (rc) hs_seterr("transpose of 8-byte elements: %s", g_err);
+    return rc ? HSFFT_ERR_DEVICE : 0;
+}
+
 /* The last transpose of hsfft_r2c_2d_full: the transposed half spectrum in[b][k1][k0] (w = n1/2 + 1
  * rows of n0) goes to the full layout out[b][k0][k1] (n0 rows of n1), and every element with
  * 1 <= k1 <= n1/2 - 1 is stored a second time, imaginary part negated, at the mirrored index
@@ -205,6 +285,8 @@ static int transpose_herm(const void *in, void *out, long long n0, long long n1,
  * fails; the last chunk may be ragged.  hsfft_exec_2d needs one copy of the chunk and
  * hsfft_exec_columns two; for the real 2D transforms the image is the half spectrum, n0 x
  * (n1/2+1) elements: hsfft_r2c_2d and hsfft_r2c_2d_full need one copy, hsfft_c2r_2d two.
+ * Images are counted in 16-byte elements: hsfft_dct_2d_batched (hsfft_dct2d.h) passes n0 x n1 / 2
+ * for its real images of n0 x n1 doubles, both even, and holds one copy.
  * `extra_elems` more elements are allocated behind the chunk copies without counting towards the
  * rule (the 2D convolution's shared kernel spectrum, hsfft_conv2d.h). */
 static void *chunk_scratch(long long img_elems, int max_dim, int copies, int batch, long long *per_chunk,
@@ -395,6 +477,27 @@ int hsfft_transpose_batched(const fft_data *d_in, fft_data *d_out, int rows, int
     if (rc) return rc;
     const int d = hs_lock_device();
     rc = tr2d::transpose(d_in, d_out, rows, cols, batch);
+    hs_unlock_device(d);
+    return rc;
+}
+
+int hsfft_transpose_real_batched(const fft_type *d_in, fft_type *d_out, int rows, int cols, int batch)
+{
+    hs_seterr("%s", "");
+    bool bad = !d_in || !d_out || d_in == d_out || batch < 0 || rows < 1 || cols < 1;
+    if (!bad) {
+        const uintptr_t bytes = sizeof(fft_type) * (uintptr_t)rows * (uintptr_t)cols * (uintptr_t)batch;
+        bad = tr2d::overlap_bytes(d_in, bytes, d_out, bytes);
+    }
+    if (bad) {
+        hs_seterr("hsfft_transpose_real_batched: invalid arguments");
+        return HSFFT_ERR_ARG;
+    }
+    if (batch == 0) return 0;
+    int rc = hs_require_gpu();
+    if (rc) return rc;
+    const int d = hs_lock_device();
+    rc = tr2d::transpose8(d_in, d_out, rows, cols, batch);
     hs_unlock_device(d);
     return rc;
 }

@@ -1541,3 +1541,4 @@ int hsd_pass_timer_read(int n, float *ms)
 #include "hsfft_filter.h"
 #include "hsfft_stft.h"
 #include "hsfft_dct.h"
+#include "hsfft_dct2d.h"

@@ -139,7 +139,10 @@ enum {
     HS_SCR_2D = 11,       /* hsfft_exec_2d / hsfft_exec_columns / the 2D real transforms (hsfft_2d.h): the
                            * chunk between the row transforms and the transposes; a class of its own,
                            * because the row transforms in between use the chain, Bluestein and
-                           * HS_SCR_REAL_Z classes */
+                           * HS_SCR_REAL_Z classes.  hsfft_dct_2d_batched (hsfft_dct2d.h) keeps its chunk
+                           * here too: the class is free there, because dct::run in between uses
+                           * HS_SCR_DCT and HS_SCR_DCT_SPEC beside those and keeps its own inner chunk
+                           * walk (HSFFT_DCT_CHUNK_MB) */
     HS_NSCRATCH = 12
 };
 void *hs_scratch(int cls, size_t bytes);

@@ -77,6 +77,8 @@ SIGNATURES = {
     "hsfft_istft_batched": (CI, [VP, VP, CI, VP, CI, CI, CI, VP, CI, CI]),
     "hsfft_dct_twiddles": (CI, [CI, VP]),
     "hsfft_dct_batched": (CI, [CI, CI, VP, VP, CI, CI]),
+    "hsfft_transpose_real_batched": (CI, [VP, VP, CI, CI, CI]),
+    "hsfft_dct_2d_batched": (CI, [CI, CI, CI, VP, VP, CI, CI, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -670,6 +672,68 @@ def idct(x, type=2):
 def idst(x, type=2):
     """inverse of dst(., type): the other type, divided by 2.0 * n in numpy (scipy.fft.idst, norm=None)"""
     return _dct_run("idst", KIND_SIN, type, x, True)
+
+
+def transpose_real_batched(d_in, d_out, rows, cols, batch):
+    """out[b][c][r] = in[b][r][c] for batch matrices of rows x cols doubles"""
+    return check(lib().hsfft_transpose_real_batched(VP(d_in.ptr), VP(d_out.ptr), rows, cols, batch),
+                 "transpose_real_batched")
+
+
+def dct_2d_batched(kind0, kind1, type, d_in, d_out, n0, n1, batch):
+    """batch real images of n0 x n1 -> batch images of n0 x n1: kind1 along the rows, then kind0 along
+    the columns (KIND_COS / KIND_SIN each), one type, 2 or 3, scipy's conventions with norm=None"""
+    return check(lib().hsfft_dct_2d_batched(kind0, kind1, type, VP(d_in.ptr), VP(d_out.ptr), n0, n1, batch),
+                 "dct_2d_batched")
+
+
+def _dctn_run(who, kind, type, x, inverse):
+    """check the shape, upload x, run hsfft_dct_2d_batched with `kind` on both axes and download;
+    inverse: the other type, then one division by 4.0 * n0 * n1 per word"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if type not in (2, 3):
+        raise ValueError(f"{who}: type is 2 or 3")
+    if x.ndim < 2:
+        raise ValueError(f"{who} needs an array of at least two dimensions")
+    n0, n1 = x.shape[-2:]
+    if n0 < 2 or n0 % 2 or n1 < 2 or n1 % 2:
+        raise ValueError(f"{who}: the last two axes are even and >= 2 long")
+    if x.size == 0:
+        return np.empty(x.shape, dtype=np.float64)
+    made = []
+    try:
+        d_in = DeviceBuffer.from_array(x)
+        made.append(d_in.free)
+        d_out = DeviceBuffer(x.nbytes)
+        made.append(d_out.free)
+        dct_2d_batched(kind, kind, 5 - type if inverse else type, d_in, d_out, n0, n1, x.size // (n0 * n1))
+        synchronize()
+        y = d_out.to_array(np.float64).reshape(x.shape)
+    finally:
+        for release in reversed(made):
+            release()
+    return y / (4.0 * n0 * n1) if inverse else y
+
+
+def dctn(x, type=2):
+    """2D DCT-II or DCT-III (scipy.fft.dctn, norm=None) over the last two axes of a float64 array of
+    shape (..., n0, n1), both even: uploads, runs hsfft_dct_2d_batched and downloads"""
+    return _dctn_run("dctn", KIND_COS, type, x, False)
+
+
+def dstn(x, type=2):
+    """2D DST-II or DST-III (scipy.fft.dstn, norm=None) over the last two axes of a float64 array"""
+    return _dctn_run("dstn", KIND_SIN, type, x, False)
+
+
+def idctn(x, type=2):
+    """inverse of dctn(., type): the other type, divided by 4.0 * n0 * n1 in numpy (scipy.fft.idctn, norm=None)"""
+    return _dctn_run("idctn", KIND_COS, type, x, True)
+
+
+def idstn(x, type=2):
+    """inverse of dstn(., type): the other type, divided by 4.0 * n0 * n1 in numpy (scipy.fft.idstn, norm=None)"""
+    return _dctn_run("idstn", KIND_SIN, type, x, True)
 
 
 def r2c_batched(rplan, d_in, d_out, batch):
