@@ -46,13 +46,15 @@ int hsfft_synchronize(void);
  * transforms that and the two buffers of HSFFT_DCT_CHUNK_MB; the overlap-add filter
  * HSFFT_FILTER_CHUNK_MB, 1 GiB; the STFT and its inverse HSFFT_STFT_CHUNK_MB, 1 GiB, in the
  * filter's first buffer; the cosine and sine transforms HSFFT_DCT_CHUNK_MB, 1 GiB, in the
- * filter's two buffers -- each halved while allocation fails).  Also frees the current device's
- * cached DCT rotation tables (at most four, rebuilt on demand). */
+ * filter's two buffers, the type-IV transforms too; the MDCT and its inverse HSFFT_MDCT_CHUNK_MB,
+ * 1 GiB, in the 2D paths' buffer beside those two -- each halved while allocation fails).  Also
+ * frees the current device's cached DCT rotation tables (at most four, rebuilt on demand) and its
+ * cached type-IV rotation tables (at most four more). */
 int hsfft_release_scratch(void);
 /* Teardown: waits for every device's work, then releases every device object the library
  * holds on every device -- scratch pool, page-locked staging slots, the device state of every
  * live plan (twiddles, odd-radix constants, Bluestein chirp / hk), real plans' device twiddles,
- * the cached DCT rotation tables, idle convolution plans, persistent-launch counters and the calling thread's error words (a
+ * the cached DCT and type-IV rotation tables, idle convolution plans, persistent-launch counters and the calling thread's error words (a
  * pending launch error of the calling thread is reported as by hsfft_synchronize), timing and
  * ordering events, the library streams.  Plans stay valid and everything is re-created on
  * demand, so the library remains usable.  Call it before process exit (bench.py and the test
@@ -392,6 +394,96 @@ int hsfft_dct_batched(int kind, int type, const fft_type *d_in, fft_type *d_out,
  * the allocation fails; the last chunk may be ragged. */
 int hsfft_dct_2d_batched(int kind0, int kind1, int type, const fft_type *d_in, fft_type *d_out, int n0, int n1,
                          int batch);
+
+/* --- batched type-IV cosine and sine transforms (DCT-IV / DST-IV) of real rows ------------ */
+/* scipy's conventions with norm=None, for rows of N = n reals:
+ *   DCT-IV   X[k] = 2 sum_n x[n] cos(pi (2k+1) (2n+1) / 4N)
+ *   DST-IV   X[k] = 2 sum_n x[n] sin(pi (2k+1) (2n+1) / 4N)
+ * so that either one applied twice gives 2N x.  Each is the unchanged c2c row transform of length
+ * N/2 with one new kernel before it and one after; there is no split pass, as the r2c of the
+ * types II and III has.  Entry points of their own: hsfft_dct_batched keeps rejecting type 4.  Only
+ * even n; type I, odd lengths, orthonormal scaling and a 2D type IV are out of scope.
+ * Host only, no device touched: the n/2 rotation words the calls below use, h_tw[j] = (c_j, s_j)
+ * for 0 <= j < n/2 from one libm sincos(PI2 * (double)(8*j + 1) / (16.0 * (double)n), &s_j, &c_j)
+ * each (the angle is pi (8j+1) / 8n; one table serves both rotations).  Returns 0, or HSFFT_ERR_ARG
+ * with a message for n odd, n < 2, n > 2^30 or a NULL h_tw. */
+int hsfft_dct4_twiddles(int n, fft_data *h_tw);
+/* kind: HSFFT_KIND_COS / HSFFT_KIND_SIN; d_in, d_out: batch contiguous rows of n reals.  The
+ * contract is compositional and bit-exact.  With N = n, h = N/2, t = the table of
+ * hsfft_dct4_twiddles(N) and a gain g = 2.0, per row (the cosine form):
+ *   a_j = x[2j], b_j = x[N-1-2j], z[j] = (a_j*c_j + b_j*s_j, b_j*c_j - a_j*s_j) for j < h,
+ *   Z = the reference's fft_exec of the forward plan fft_init(h, 1) on z (h == 1: a copy),
+ *   re_k = Z[k].re*c_k + Z[k].im*s_k, im_k = Z[k].im*c_k - Z[k].re*s_k,
+ *   out[2k] = g*re_k, out[N-1-2k] = (-g)*im_k for k < h,
+ * every multiply, add and subtract rounded on its own and computed for every index with no
+ * special case.  The sine form is the cosine form of the reversed row, x'[n] = x[N-1-n], with the
+ * sign bit of the odd outputs flipped (of zeros and NaNs too): an index and sign variant inside the
+ * same two kernels, with no extra pass over memory.  Where two NaN terms meet in one add, the
+ * payload is not part of the contract; everything else is.
+ * The plan comes from the convolution plan cache: it follows the calling thread's twiddle mode, and
+ * a repeated length builds nothing.  Any even n (mixed-radix or Bluestein h, h == 1); Bluestein h
+ * keep the error-word contract of hsfft_exec_batched (below).
+ * Asynchronous on the library stream under the device lock; the input is never written; every
+ * output word is written exactly once and none is read; caller rows need the alignment of a
+ * double only.  Returns 0 on success and for batch == 0.  HSFFT_ERR_ARG with a message -- before any
+ * device is touched -- for a kind other than 0 or 1, n odd, n < 2 or n > 2^30, batch < 0, n x batch >
+ * 2^40, NULL pointers, d_in == d_out or input and output byte ranges that overlap.
+ * Scratch: the two pool buffers of hsfft_dct_batched, N/2 complex per row each, no allocation per
+ * call.  Rows are walked in chunks of HSFFT_DCT_CHUNK_MB / (N x 16) rows (default 1024 MiB, at
+ * least 1, read per call), at least one, halved while the allocation fails.  The table is cached on
+ * the device in a cache of its own, four lengths per device, the least recently used one replaced:
+ * a length not in the cache builds its table on the host and uploads it synchronously. */
+int hsfft_dct4_batched(int kind, const fft_type *d_in, fft_type *d_out, int n, int batch);
+
+/* --- batched MDCT and IMDCT of real rows -------------------------------------------------- */
+/* The lapped transform of audio codecs: frames of 2N samples, N apart (N even, 2 to 2^30), N
+ * coefficients per frame; a window d_w of 2N reals, or NULL for none.
+ *   forward   X[k] = sum_{m<2N} u[m] cos(pi/N (m + 1/2 + N/2) (k + 1/2)),   u = frame x window
+ *   backward  y[m] = the same sum over k < N
+ * With pad == 0 frame f starts at sample f N; with pad == 1 at f N - N, so that the first and the
+ * last N samples of a row lie in two frames as well; lpad = pad ? N : 0, and a position outside
+ * [0, n) reads +0.0.
+ * Sizes only, no device touched: n % N == 0 is required; pad == 0 needs n >= 2N and gives nframes =
+ * n/N - 1, pad == 1 needs n >= N and gives nframes = n/N + 1.  nframes and lpad may be NULL.
+ * HSFFT_ERR_ARG with a message for anything else, N odd, N < 2, N or n above 2^30, n < 1, or a pad
+ * other than 0 or 1. */
+int hsfft_mdct_shape(int n, int N, int pad, int *nframes, int *lpad);
+/* d_x: batch rows of n reals; d_out: batch x nframes x N reals, frame-major.  Bit-exact contract,
+ * frame f of row b, q = N/2:
+ *   p[m] = xpad[f N - lpad + m] * w[m], one multiply (computed on the +0.0 outside the row too); no
+ *       multiply for a NULL d_w,
+ *   u[i] = (-p[3q-1-i]) - p[3q+i] for i < q, u[i] = p[i-q] - p[3q-1-i] for q <= i < N, the unary
+ *       minus a flip of the sign bit,
+ *   out[b][f][:] = the hsfft_dct4_batched contract (cosine) on u with the gain g = 1.0.
+ * One kernel gathers, windows and folds into a scratch of rows of N; the type-IV driver runs from
+ * there into d_out.  Asynchronous like hsfft_dct4_batched; inputs are never written.  Returns 0 on
+ * success and for batch == 0.  HSFFT_ERR_ARG with a message -- before any device is touched -- for
+ * what hsfft_mdct_shape rejects, NULL d_x or d_out, batch < 0, nframes x batch > 2^31 - 1, n x batch
+ * or nframes x batch x N above 2^40, or a d_out range that overlaps d_x's or d_w's.
+ * Scratch: the 2D transforms' pool buffer, beside the two of hsfft_dct4_batched (walked in chunks of
+ * their own).  Consecutive frames b nframes + f are walked in chunks of HSFFT_MDCT_CHUNK_MB / (N x 8)
+ * frames (default 1024 MiB, at least 1, read per call), at least one, halved while the allocation
+ * fails; a chunk may cross rows. */
+int hsfft_mdct_batched(const fft_type *d_x, int n, const fft_type *d_w, int N, int pad, fft_type *d_out, int batch);
+/* d_X: batch x nframes x N coefficients; d_out: batch rows of n = (nframes + 1) N - 2 lpad reals,
+ * n >= 1 (so pad == 1 needs nframes >= 2).  Bit-exact contract, q = N/2:
+ *   v_f = the hsfft_dct4_batched contract (cosine) on frame f's coefficients with g = 1.0,
+ *   y_f[m] = v_f[m+q] for m < q, -v_f[3q-1-m] for q <= m < 3q, -v_f[m-3q] for 3q <= m < 2N (sign-bit
+ *       flips),
+ *   t_f[m] = (y_f[m] / (double)q) * w[m]: one division and one multiply, the multiply absent for a
+ *       NULL d_w,
+ *   out[b][i], with P = i + lpad: the term t_f[P - f N] of the earlier covering frame f = P/N - 1 where
+ *       that is >= 0, then the term of frame P/N added where that is < nframes; a single covering
+ *       frame gives its term alone, not 0.0 + term.
+ * With a Princen-Bradley window, w[m]^2 + w[m+N]^2 = 1, the division by N/2 makes imdct(mdct(x))
+ * equal x on every sample that two frames cover.  One kernel reads the two v rows per sample and
+ * writes every output word exactly once, with no atomics.  Conventions and rejections as for
+ * hsfft_mdct_batched, with nframes >= 1 and n equal to the length above.
+ * Scratch: the same buffers.  Whole rows are walked in chunks of HSFFT_MDCT_CHUNK_MB / (nframes x N
+ * x 8) rows, at least one, halved while the allocation fails; one row larger than the knob still
+ * runs as one chunk. */
+int hsfft_imdct_batched(const fft_type *d_X, int nframes, const fft_type *d_w, int N, int pad, fft_type *d_out, int n,
+                        int batch);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */

@@ -344,6 +344,7 @@ int hsfft_release_scratch(void)
             g_scr_sz[d][c] = 0;
         }
         hs_dct_release_device(d);
+        hs_dct4_release_device(d);
     }
     hs_unlock_device(d);
     return rc;
@@ -463,6 +464,7 @@ int hsfft_finalize(void)
         pthread_mutex_unlock(&g_lock);
         hs_real_release_device(d);
         hs_dct_release_device(d);
+        hs_dct4_release_device(d);
         const int fr = hsd_finalize_device();
         if (fr && !rc) {
             hs_seterr("hsfft_finalize: %s", hsd_errstr());

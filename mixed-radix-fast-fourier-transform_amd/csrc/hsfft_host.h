@@ -143,6 +143,11 @@ enum {
                            * here too: the class is free there, because dct::run in between uses
                            * HS_SCR_DCT and HS_SCR_DCT_SPEC beside those and keeps its own inner chunk
                            * walk (HSFFT_DCT_CHUNK_MB) */
+    HS_SCR_MDCT = 11,     /* hsfft_mdct_batched / hsfft_imdct_batched (hsfft_dct4.h): a chunk's folded frames,
+                           * or its frames after the type-IV transform.  The 2D class under a second
+                           * name by the argument of hsfft_dct_2d_batched: dct4::run in between uses
+                           * HS_SCR_DCT and HS_SCR_DCT_SPEC beside the row kernels' classes and keeps its
+                           * own inner chunk walk, and no 2D entry point is called from here */
     HS_NSCRATCH = 12
 };
 void *hs_scratch(int cls, size_t bytes);
@@ -190,6 +195,11 @@ void hs_real_release_device(int dev);
 #define HS_DCT_MAX_LEN (1 << 30)
 const void *hs_dct_table(int dev, int n);
 void hs_dct_release_device(int dev);
+/* The type-IV transforms' rotation table (hsfft_dct4.c), n/2 words (cos, sin)(pi (8j+1) / 8n), with
+ * a cache of its own under the same rules: four lengths per device, the least recently used one
+ * replaced, freed by hs_dct4_release_device and rebuilt on demand. */
+const void *hs_dct4_table(int dev, int n);
+void hs_dct4_release_device(int dev);
 /* bytes from an environment knob given in MiB (default dflt_mb; at least 1 MiB) */
 size_t hs_env_mb(const char *name, double dflt_mb);
 

@@ -79,6 +79,11 @@ SIGNATURES = {
     "hsfft_dct_batched": (CI, [CI, CI, VP, VP, CI, CI]),
     "hsfft_transpose_real_batched": (CI, [VP, VP, CI, CI, CI]),
     "hsfft_dct_2d_batched": (CI, [CI, CI, CI, VP, VP, CI, CI, CI]),
+    "hsfft_dct4_twiddles": (CI, [CI, VP]),
+    "hsfft_dct4_batched": (CI, [CI, VP, VP, CI, CI]),
+    "hsfft_mdct_shape": (CI, [CI, CI, CI, ctypes.POINTER(CI), ctypes.POINTER(CI)]),
+    "hsfft_mdct_batched": (CI, [VP, CI, VP, CI, CI, VP, CI]),
+    "hsfft_imdct_batched": (CI, [VP, CI, VP, CI, CI, VP, CI, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -734,6 +739,135 @@ def idctn(x, type=2):
 def idstn(x, type=2):
     """inverse of dstn(., type): the other type, divided by 4.0 * n0 * n1 in numpy (scipy.fft.idstn, norm=None)"""
     return _dctn_run("idstn", KIND_SIN, type, x, True)
+
+
+def dct4_twiddles(n):
+    """the n/2 rotation words (cos, sin)(pi (8j+1) / 8n) of hsfft_dct4_batched as complex128: host only"""
+    t = np.empty(max(int(n), 0) // 2, dtype=np.complex128)
+    check(lib().hsfft_dct4_twiddles(n, _ptr(t)), "dct4_twiddles")
+    return t
+
+
+def dct4_batched(kind, d_in, d_out, n, batch):
+    """batch real rows of n samples -> batch rows of n: DCT-IV (KIND_COS) or DST-IV (KIND_SIN),
+    scipy's conventions with norm=None"""
+    return check(lib().hsfft_dct4_batched(kind, VP(d_in.ptr), VP(d_out.ptr), n, batch), "dct4_batched")
+
+
+def mdct_shape(n, N, pad=False):
+    """(nframes, lpad) of hsfft_mdct_batched: sizes only, no device touched"""
+    v = [CI(0) for _ in range(2)]
+    check(lib().hsfft_mdct_shape(n, N, int(pad), *(ctypes.byref(x) for x in v)), "mdct_shape")
+    return tuple(x.value for x in v)
+
+
+def mdct_batched(d_x, n, d_w, N, pad, d_out, batch):
+    """batch real rows of n samples -> batch x nframes x N coefficients: frames of 2N samples N
+    apart, times the window d_w of 2N (None: no window)"""
+    return check(lib().hsfft_mdct_batched(VP(d_x.ptr), n, _opt_ptr(d_w), N, int(pad), VP(d_out.ptr), batch), "mdct_batched")
+
+
+def imdct_batched(d_X, nframes, d_w, N, pad, d_out, n, batch):
+    """batch x nframes x N coefficients -> batch real rows of n = (nframes + 1) N - 2 lpad samples:
+    every frame's 2N samples / (N/2), times the window, overlap-added"""
+    return check(lib().hsfft_imdct_batched(VP(d_X.ptr), nframes, _opt_ptr(d_w), N, int(pad), VP(d_out.ptr), n, batch),
+                 "imdct_batched")
+
+
+def _device_run(call, x, window, out_shape):
+    """upload x and the window, run call(d_x, d_w, d_out), download float64 of out_shape"""
+    made = []
+    try:
+        d_x = DeviceBuffer.from_array(x)
+        made.append(d_x.free)
+        d_w = None
+        if window is not None:
+            d_w = DeviceBuffer.from_array(window)
+            made.append(d_w.free)
+        d_out = DeviceBuffer(int(np.prod(out_shape)) * 8)
+        made.append(d_out.free)
+        call(d_x, d_w, d_out)
+        synchronize()
+        return d_out.to_array(np.float64).reshape(out_shape)
+    finally:
+        for release in reversed(made):
+            release()
+
+
+def _mdct_window(who, window, N):
+    if window is None:
+        return None
+    window = np.ascontiguousarray(window, dtype=np.float64)
+    if window.shape != (2 * N,):
+        raise ValueError(f"{who}: the window is one-dimensional, 2 N = {2 * N} long")
+    return window
+
+
+def _dct4_run(who, kind, x):
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim not in (1, 2):
+        raise ValueError(f"{who} needs x of one or two dimensions")
+    n = x.shape[-1]
+    if n < 2 or n % 2:
+        raise ValueError(f"{who}: the row length is even and >= 2")
+    if x.size == 0:
+        return np.empty(x.shape, dtype=np.float64)
+    return _device_run(lambda d_x, d_w, d_out: dct4_batched(kind, d_x, d_out, n, x.size // n), x, None, x.shape)
+
+
+def dct4(x):
+    """DCT-IV (scipy.fft.dct(x, type=4), norm=None) of the float64 rows x, of shape (n,) or (batch, n),
+    n even; its own inverse up to 2n: uploads, runs hsfft_dct4_batched and downloads"""
+    return _dct4_run("dct4", KIND_COS, x)
+
+
+def dst4(x):
+    """DST-IV (scipy.fft.dst(x, type=4), norm=None) of the float64 rows x, of shape (n,) or (batch, n)"""
+    return _dct4_run("dst4", KIND_SIN, x)
+
+
+def mdct(x, N, window=None, pad=False):
+    """MDCT of the float64 rows x, of shape (n,) or (batch, n), n a multiple of the hop N (even):
+    float64 (batch, nframes, N), without the batch axis for 1-D input; frames of 2N samples N apart
+    times `window` (2N long).  pad=True adds one frame at either end, so that every sample lies in
+    two frames.  Uploads, runs hsfft_mdct_batched and downloads"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    pad = bool(pad)
+    if x.ndim not in (1, 2):
+        raise ValueError("mdct needs x of one or two dimensions")
+    if N < 2 or N % 2:
+        raise ValueError("mdct: the hop N is even and >= 2")
+    n = x.shape[-1]
+    if n % N or n < (N if pad else 2 * N):
+        raise ValueError("mdct: a row is a multiple of N long and holds at least one frame of 2N (N with pad)")
+    window = _mdct_window("mdct", window, N)
+    nframes = n // N + 1 if pad else n // N - 1
+    shape = x.shape[:-1] + (nframes, N)
+    if x.size == 0:
+        return np.empty(shape, dtype=np.float64)
+    if nframes != mdct_shape(n, N, pad)[0]:
+        raise HsfftError("mdct: the library's frame count differs from the binding's")
+    return _device_run(lambda d_x, d_w, d_out: mdct_batched(d_x, n, d_w, N, pad, d_out, x.size // n), x, window, shape)
+
+
+def imdct(X, window=None, pad=False):
+    """inverse of mdct for float64 X of shape (nframes, N) or (batch, nframes, N): rows of (nframes +
+    1) N samples, 2N fewer with pad; with a window whose squares N apart add up to one, imdct(mdct(x))
+    is x on every sample that two frames cover.  Uploads, runs hsfft_imdct_batched and downloads"""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    pad = bool(pad)
+    if X.ndim not in (2, 3):
+        raise ValueError("imdct needs X of two or three dimensions")
+    nframes, N = X.shape[-2:]
+    if N < 2 or N % 2 or nframes < (2 if pad else 1):
+        raise ValueError("imdct: N is even and >= 2, and there is at least one frame (two with pad)")
+    window = _mdct_window("imdct", window, N)
+    n = (nframes + 1) * N - (2 * N if pad else 0)
+    shape = X.shape[:-2] + (n,)
+    if X.size == 0:
+        return np.empty(shape, dtype=np.float64)
+    batch = X.size // (nframes * N)
+    return _device_run(lambda d_X, d_w, d_out: imdct_batched(d_X, nframes, d_w, N, pad, d_out, n, batch), X, window, shape)
 
 
 def r2c_batched(rplan, d_in, d_out, batch):
