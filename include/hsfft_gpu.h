@@ -47,14 +47,16 @@ int hsfft_synchronize(void);
  * HSFFT_FILTER_CHUNK_MB, 1 GiB; the STFT and its inverse HSFFT_STFT_CHUNK_MB, 1 GiB, in the
  * filter's first buffer; the cosine and sine transforms HSFFT_DCT_CHUNK_MB, 1 GiB, in the
  * filter's two buffers, the type-IV transforms too; the MDCT and its inverse HSFFT_MDCT_CHUNK_MB,
- * 1 GiB, in the 2D paths' buffer beside those two -- each halved while allocation fails).  Also
- * frees the current device's cached DCT rotation tables (at most four, rebuilt on demand) and its
- * cached type-IV rotation tables (at most four more). */
+ * 1 GiB, in the 2D paths' buffer beside those two; the chirp-z transforms HSFFT_CZT_CHUNK_MB, 1 GiB,
+ * in the cosine and sine transforms' two buffers -- each halved while allocation fails).  Also
+ * frees the current device's cached DCT rotation tables (at most four, rebuilt on demand), its
+ * cached type-IV rotation tables (at most four more) and its cached chirp-z entries (at most four:
+ * the tables, the wrapped chirp and its spectrum; hs_czt_release_device). */
 int hsfft_release_scratch(void);
 /* Teardown: waits for every device's work, then releases every device object the library
  * holds on every device -- scratch pool, page-locked staging slots, the device state of every
  * live plan (twiddles, odd-radix constants, Bluestein chirp / hk), real plans' device twiddles,
- * the cached DCT and type-IV rotation tables, idle convolution plans, persistent-launch counters and the calling thread's error words (a
+ * the cached DCT and type-IV rotation tables, the cached chirp-z entries (hs_czt_release_device), idle convolution plans, persistent-launch counters and the calling thread's error words (a
  * pending launch error of the calling thread is reported as by hsfft_synchronize), timing and
  * ordering events, the library streams.  Plans stay valid and everything is re-created on
  * demand, so the library remains usable.  Call it before process exit (bench.py and the test
@@ -484,6 +486,62 @@ int hsfft_mdct_batched(const fft_type *d_x, int n, const fft_type *d_w, int N, i
  * runs as one chunk. */
 int hsfft_imdct_batched(const fft_type *d_X, int nframes, const fft_type *d_w, int N, int pad, fft_type *d_out, int n,
                         int batch);
+
+/* --- batched chirp-z transform (zoom FFT) of real and complex rows -------------------------- */
+/* m bins at any spacing df, starting at any frequency f0 (doubles, in cycles per sample), of a row
+ * x of n samples, real or complex:
+ *   X[k] = sum_{j<n} x[j] exp(-2 pi i j (f0 + k df)),   0 <= k < m
+ * scipy.signal.zoom_fft(x, [f1, f2], m, fs) is f0 = f1/fs, df = (f2-f1)/(m fs); scipy.signal.czt(x, m, w,
+ * a) on the unit circle is w = exp(-2 pi i df), a = exp(2 pi i f0); n = m, f0 = 0, df = 1/n is the
+ * forward DFT.  Bluestein's algorithm: the unchanged c2c row transforms of the power-of-two length L
+ * with one new kernel before, one between and one after.  Spiral contours (|w| or |a| other than 1),
+ * an inverse and 2D are out of scope.
+ * Sizes only, no device touched: L = max(2, the power of two >= n + m - 1); L may be NULL.
+ * HSFFT_ERR_ARG with a message unless n >= 1, m >= 1 and n + m - 1 <= 2^26 (every j < max(n, m) then
+ * has j*j exact in a double). */
+int hsfft_czt_shape(int n, int m, int *L);
+/* Host only, no device touched: the K = max(n, m) chirp words and the n input-rotation words the
+ * calls below use, each (c, s) from one libm sincos(PI2 * (0.5 * ph), &s, &c).  The phase ph, in
+ * half-turns, comes from this reduction, which is part of the contract:
+ *   red(a, b):  p = a*b (rounded);  e = fma(a, b, -p) (the product's exact error);
+ *               return fmod(p, 2.0) + e          (fmod is exact; one rounded add)
+ *   h_chirp[j]: ph = red((double)j*(double)j, df)                               0 <= j < K
+ *   h_pre[j]:   ph = red((double)(2*j), f0) + red((double)j*(double)j, df)      0 <= j < n
+ * so the phase j*j*df, which in plain double loses bits as j grows, keeps its full precision modulo
+ * one turn; with f0 == 0, h_pre[j] equals h_chirp[j] bit for bit.  Either pointer may be NULL and is
+ * then skipped.  HSFFT_ERR_ARG with a message for what hsfft_czt_shape rejects and for an f0 or df
+ * that is not finite or above 1 in magnitude (frequencies are periodic: callers reduce them). */
+int hsfft_czt_tables(int n, int m, double f0, double df, fft_data *h_pre, fft_data *h_chirp);
+/* d_in: batch contiguous rows of n complex (hsfft_czt_batched) or n reals (hsfft_czt_real_batched);
+ * d_out: batch rows of m complex.  The contract is compositional and bit-exact.  With f = fft_init(L,
+ * 1) and g = fft_init(L, -1) from the convolution plan cache (they follow the calling thread's
+ * twiddle mode) and (c, s) table words of hsfft_czt_tables, per row:
+ *   u[j] = (x.re*c + x.im*s, x.im*c - x.re*s) with (c, s) = pre[j], j < n;  (+0.0, +0.0) for n <= j < L
+ *          real input: u[j] = (x*c, -(x*s)), the minus a flip of the sign bit: two multiplies, no add
+ *   v[i] = chirp[i] for i < m;  v[L-j] = chirp[j] for 1 <= j < n;  (+0.0, +0.0) elsewhere
+ *   V    = the reference's fft_exec(f) on v -- once per (n, m, f0, df, twiddle mode), not per row
+ *   U    = the reference's fft_exec(f) on u
+ *   P[i] = (U.re*V.re - U.im*V.im, U.re*V.im + U.im*V.re)
+ *   y    = the reference's fft_exec(g) on P
+ *   d    = (y[k].re / (double)L, y[k].im / (double)L)
+ *   X[k] = (d.re*c + d.im*s, d.im*c - d.re*s) with (c, s) = chirp[k],  k < m
+ * every multiply, add, subtract and divide rounded on its own and computed for every index with no
+ * special case.  Where two NaN terms meet in one add, the payload is not part of the contract;
+ * everything else is.
+ * Asynchronous on the library stream under the device lock; the input is never written; every
+ * output word is written exactly once and none is read; caller rows need the alignment of a
+ * double only.  Returns 0 on success and for batch == 0.  HSFFT_ERR_ARG with a message -- before any
+ * device is touched -- for what hsfft_czt_shape or hsfft_czt_tables rejects, NULL pointers, batch < 0,
+ * n x batch, m x batch or L x batch above 2^40, or input and output byte ranges that overlap (each
+ * with its own element size).
+ * Scratch: the two pool buffers of hsfft_dct_batched, L complex per row each, no allocation per
+ * call.  Rows are walked in chunks of HSFFT_CZT_CHUNK_MB / (2 x L x 16) rows (default 1024 MiB, at
+ * least 1, read per call), at least one, halved while the allocation fails; HSFFT_ERR_NOMEM if one
+ * row still fails.  pre, chirp, v and V are cached on the device, four (n, m, f0, df, twiddle mode)
+ * per device, the least recently used one replaced: a transform not in the cache builds its tables
+ * on the host, uploads them synchronously and runs the one transform of v before the first row. */
+int hsfft_czt_batched(const fft_data *d_in, int n, fft_data *d_out, int m, double f0, double df, int batch);
+int hsfft_czt_real_batched(const fft_type *d_in, int n, fft_data *d_out, int m, double f0, double df, int batch);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */

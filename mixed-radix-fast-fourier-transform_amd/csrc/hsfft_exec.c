@@ -345,6 +345,7 @@ int hsfft_release_scratch(void)
         }
         hs_dct_release_device(d);
         hs_dct4_release_device(d);
+        hs_czt_release_device(d);
     }
     hs_unlock_device(d);
     return rc;
@@ -422,7 +423,7 @@ static int pin_reserve(void *pin[2], size_t *sz, size_t bytes)
 /* Teardown (include/hsfft_gpu.h): every device object the library holds, on every device,
  * after waiting for that device's work -- the scratch pool, the page-locked staging slots, the
  * device state of every live plan (twiddles, odd-radix constants, Bluestein chirp / hk), the
- * real plans' device twiddles, the idle convolution plan pairs, the persistent-launch counters
+ * real plans' device twiddles, the cached rotation tables and chirp-z entries, the idle convolution plan pairs, the persistent-launch counters
  * and error words, the calling thread's own slots / words / streams, the timing and ordering
  * events and the library streams.  Everything is re-created on demand.  Callers must not run
  * other library calls concurrently. */
@@ -465,6 +466,7 @@ int hsfft_finalize(void)
         hs_real_release_device(d);
         hs_dct_release_device(d);
         hs_dct4_release_device(d);
+        hs_czt_release_device(d);
         const int fr = hsd_finalize_device();
         if (fr && !rc) {
             hs_seterr("hsfft_finalize: %s", hsd_errstr());

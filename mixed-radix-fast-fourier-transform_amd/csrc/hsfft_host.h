@@ -122,6 +122,11 @@ enum {
                            * c2r.  A third name for the same number by the same argument: the call is
                            * asynchronous, runs wholly on the library stream under the device lock and
                            * calls neither the filter nor the STFT, so stream order separates the users */
+    HS_SCR_CZT = 2,       /* hsfft_czt_batched / hsfft_czt_real_batched (hsfft_czt.h): a chunk's rotated, zero-filled
+                           * rows, then its rows after the inverse transform.  A fourth name for the same
+                           * number by the same argument: the call is asynchronous, runs wholly on the
+                           * library stream under the device lock and calls neither the filter, the STFT
+                           * nor a cosine or sine transform, so stream order separates the users */
     HS_SCR_BLUE_MID = 3,  /* Bluestein M-point intermediate, or the persistent launch's images */
     HS_SCR_REAL_Z = 4,    /* real transforms: the inner c2c's N/2-point rows */
     HS_SCR_STAGE_IN = 5,  /* drop-in fft_exec / fft_r2c_exec / fft_c2r_exec: staged input */
@@ -135,6 +140,9 @@ enum {
     HS_SCR_CONV_SPEC = 10,/* convolution: both compact spectra */
     HS_SCR_DCT_SPEC = 10, /* hsfft_dct_batched: a chunk's compact spectra, as the filter keeps its own in
                            * HS_SCR_CONV_SPEC; the convolution, the filter and this call all run on the
+                           * library stream under the device lock and never call each other */
+    HS_SCR_CZT_SPEC = 10, /* the chirp-z calls: a chunk's spectra, then their products with the chirp's, as
+                           * hsfft_dct_batched keeps its spectra here: all users of the number run on the
                            * library stream under the device lock and never call each other */
     HS_SCR_2D = 11,       /* hsfft_exec_2d / hsfft_exec_columns / the 2D real transforms (hsfft_2d.h): the
                            * chunk between the row transforms and the transposes; a class of its own,
@@ -200,6 +208,25 @@ void hs_dct_release_device(int dev);
  * replaced, freed by hs_dct4_release_device and rebuilt on demand. */
 const void *hs_dct4_table(int dev, int n);
 void hs_dct4_release_device(int dev);
+/* The chirp-z transform's host side (hsfft_czt.c).  hs_czt_sizes and hs_czt_freqs: the argument
+ * rules of hsfft_czt_shape and hsfft_czt_tables for the other entry points; 0, or HSFFT_ERR_ARG with
+ * the message set.  hs_czt_get (device lock of `dev` held, `dev` current): the device data of one (n,
+ * m, f0, df, twiddle mode) from a cache of four per device, the least recently used one replaced (it
+ * is waited for before it is freed); a miss builds the two tables and the wrapped chirp v on the
+ * host and uploads them synchronously, and leaves `ready` 0: the driver then transforms v into V
+ * and calls hs_czt_set_ready.  0, or HSFFT_ERR_NOMEM with the message set.  hs_czt_release_device
+ * (the same lock held, the device's work waited for): frees the device's entries. */
+#define HS_CZT_MAX_SUM (1 << 26)
+typedef struct {
+    const fft_data *pre, *chirp, *v; /* n, max(n, m) and L words */
+    fft_data *V;                     /* L words: the forward transform of v once `ready` */
+    int slot, ready;
+} hs_czt_data;
+int hs_czt_sizes(const char *who, int n, int m, int *L);
+int hs_czt_freqs(const char *who, double f0, double df);
+int hs_czt_get(int dev, int n, int m, int L, double f0, double df, int mode, hs_czt_data *out);
+void hs_czt_set_ready(int dev, int slot);
+void hs_czt_release_device(int dev);
 /* bytes from an environment knob given in MiB (default dflt_mb; at least 1 MiB) */
 size_t hs_env_mb(const char *name, double dflt_mb);
 

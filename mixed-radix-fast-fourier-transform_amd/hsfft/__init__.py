@@ -84,6 +84,10 @@ SIGNATURES = {
     "hsfft_mdct_shape": (CI, [CI, CI, CI, ctypes.POINTER(CI), ctypes.POINTER(CI)]),
     "hsfft_mdct_batched": (CI, [VP, CI, VP, CI, CI, VP, CI]),
     "hsfft_imdct_batched": (CI, [VP, CI, VP, CI, CI, VP, CI, CI]),
+    "hsfft_czt_shape": (CI, [CI, CI, ctypes.POINTER(CI)]),
+    "hsfft_czt_tables": (CI, [CI, CI, ctypes.c_double, ctypes.c_double, VP, VP]),
+    "hsfft_czt_batched": (CI, [VP, CI, VP, CI, ctypes.c_double, ctypes.c_double, CI]),
+    "hsfft_czt_real_batched": (CI, [VP, CI, VP, CI, ctypes.c_double, ctypes.c_double, CI]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -868,6 +872,85 @@ def imdct(X, window=None, pad=False):
         return np.empty(shape, dtype=np.float64)
     batch = X.size // (nframes * N)
     return _device_run(lambda d_X, d_w, d_out: imdct_batched(d_X, nframes, d_w, N, pad, d_out, n, batch), X, window, shape)
+
+
+def czt_shape(n, m):
+    """the padded power-of-two length L = max(2, next power of two >= n + m - 1) of the chirp-z
+    calls: sizes only, no device touched"""
+    L = CI(0)
+    check(lib().hsfft_czt_shape(n, m, ctypes.byref(L)), "czt_shape")
+    return L.value
+
+
+def czt_tables(n, m, f0, df):
+    """(pre, chirp) of hsfft_czt_batched as complex128 (cos + i sin): the n input-rotation words and
+    the max(n, m) chirp words, phases reduced exactly: host only"""
+    n, m = int(n), int(m)
+    pre = np.empty(max(n, 0), dtype=np.complex128)
+    chirp = np.empty(max(n, m, 0), dtype=np.complex128)
+    check(lib().hsfft_czt_tables(n, m, f0, df, _ptr(pre), _ptr(chirp)), "czt_tables")
+    return pre, chirp
+
+
+def czt_batched(d_in, real, n, d_out, m, f0, df, batch):
+    """batch rows of n samples, float64 (real true) or complex128 -> batch rows of m complex:
+    X[k] = sum_j x[j] exp(-2 pi i j (f0 + k df)), f0 and df in cycles per sample"""
+    fn = lib().hsfft_czt_real_batched if real else lib().hsfft_czt_batched
+    return check(fn(VP(d_in.ptr), n, VP(d_out.ptr), m, f0, df, batch), "czt_real_batched" if real else "czt_batched")
+
+
+def czt(x, m, f0, df):
+    """chirp-z transform on the unit circle of the rows x, float64 or complex128 of shape (n,) or
+    (batch, n): complex128 (batch, m), without the batch axis for 1-D input, X[k] = sum_j x[j]
+    exp(-2 pi i j (f0 + k df)).  scipy.signal.czt(x, m, w, a) with w = exp(-2 pi i df), a = exp(2 pi i
+    f0).  Uploads, runs hsfft_czt_batched or hsfft_czt_real_batched (picked by the dtype) and downloads"""
+    x = np.asarray(x)
+    if x.ndim not in (1, 2):
+        raise ValueError("czt needs x of one or two dimensions")
+    real = not np.iscomplexobj(x)
+    x = np.ascontiguousarray(x, dtype=np.float64 if real else np.complex128)
+    n, m = x.shape[-1], int(m)
+    if n < 1 or m < 1 or n + m - 1 > 1 << 26:
+        raise ValueError("czt: n and m are at least 1 and n + m - 1 is at most 2^26")
+    f0, df = float(f0), float(df)
+    if not (abs(f0) <= 1.0 and abs(df) <= 1.0):
+        raise ValueError("czt: f0 and df are finite and at most 1 in magnitude (frequencies are periodic: reduce them)")
+    shape = x.shape[:-1] + (m,)
+    if x.size == 0:
+        return np.empty(shape, dtype=np.complex128)
+    made = []
+    try:
+        d_x = DeviceBuffer.from_array(x)
+        made.append(d_x.free)
+        d_out = DeviceBuffer(int(np.prod(shape)) * 16)
+        made.append(d_out.free)
+        czt_batched(d_x, real, n, d_out, m, f0, df, x.size // n)
+        synchronize()
+        return d_out.to_array(np.complex128).reshape(shape)
+    finally:
+        for release in reversed(made):
+            release()
+
+
+def zoom_fft(x, fn, m=None, fs=2.0, endpoint=False):
+    """scipy.signal.zoom_fft: m bins of the rows x from f1 to f2 (fn = [f1, f2], or a scalar f2 with f1 =
+    0) at the sampling frequency fs; m defaults to the row length, and endpoint=True includes f2.  It is
+    czt(x, m, f1 / fs, (f2 - f1) / (d fs)) with d = m - 1 for endpoint, else m"""
+    x = np.asarray(x)
+    if x.ndim not in (1, 2):
+        raise ValueError("zoom_fft needs x of one or two dimensions")
+    m = x.shape[-1] if m is None else int(m)
+    if m < 1:
+        raise ValueError("zoom_fft: m is at least 1")
+    fn = np.atleast_1d(np.asarray(fn, dtype=np.float64))
+    if fn.shape == (1,):
+        f1, f2 = 0.0, float(fn[0])
+    elif fn.shape == (2,):
+        f1, f2 = float(fn[0]), float(fn[1])
+    else:
+        raise ValueError("zoom_fft: fn is a scalar or holds two frequencies")
+    d = m - 1 if endpoint else m
+    return czt(x, m, f1 / fs, (f2 - f1) / (d * fs) if d else 0.0)
 
 
 def r2c_batched(rplan, d_in, d_out, batch):
