@@ -48,7 +48,8 @@ int hsfft_synchronize(void);
  * filter's first buffer; the cosine and sine transforms HSFFT_DCT_CHUNK_MB, 1 GiB, in the
  * filter's two buffers, the type-IV transforms too; the MDCT and its inverse HSFFT_MDCT_CHUNK_MB,
  * 1 GiB, in the 2D paths' buffer beside those two; the chirp-z transforms HSFFT_CZT_CHUNK_MB, 1 GiB,
- * in the cosine and sine transforms' two buffers -- each halved while allocation fails).  Also
+ * in the cosine and sine transforms' two buffers; the analytic signal and Fourier resampling
+ * HSFFT_SPECTRAL_CHUNK_MB, 1 GiB, in the same two buffers -- each halved while allocation fails).  Also
  * frees the current device's cached DCT rotation tables (at most four, rebuilt on demand), its
  * cached type-IV rotation tables (at most four more) and its cached chirp-z entries (at most four:
  * the tables, the wrapped chirp and its spectrum; hs_czt_release_device). */
@@ -542,6 +543,65 @@ int hsfft_czt_tables(int n, int m, double f0, double df, fft_data *h_pre, fft_da
  * on the host, uploads them synchronously and runs the one transform of v before the first row. */
 int hsfft_czt_batched(const fft_data *d_in, int n, fft_data *d_out, int m, double f0, double df, int batch);
 int hsfft_czt_real_batched(const fft_type *d_in, int n, fft_data *d_out, int m, double f0, double df, int batch);
+
+/* --- batched analytic signal (Hilbert) and Fourier resampling of real rows ----------------- */
+/* scipy.signal.hilbert(x) = x + i H[x], and scipy.signal.resample(x, m): the sample count of a row
+ * changed from n to m by truncating or zero-extending its spectrum.  Both are the unchanged r2c row
+ * transform of length n, one new kernel that edits the compact spectrum, and the unchanged inverse
+ * row transform -- c2c of n words, or c2r of m reals -- which writes straight into d_out; the edit is
+ * not fused into a transform pass.  n and m are even, from 2 to 2^30 (the limit of hsfft_dct_batched;
+ * the row transforms have no lower one): a real plan needs an even length.  Odd lengths, a window
+ * in the frequency domain, complex rows and other axes are out of scope.
+ * The contract is compositional and bit-exact.  With f = fft_real_init(n, 1), S = the n/2+1 compact
+ * bins of the reference's fft_r2c_exec(f) on the row -- the words hsfft_r2c_batched_compact writes --
+ * and q(a) = a / (double)n applied per component, one correctly rounded IEEE division (not a
+ * multiply by a reciprocal):
+ * hsfft_hilbert_batched, d_in: batch rows of n reals, d_out: batch rows of n complex:
+ *   Z[0] = q(S[0]);  Z[k] = q(S[k] + S[k]) for 0 < k < n/2 (the add per component, before the
+ *   division);  Z[n/2] = q(S[n/2]);  Z[k] = (+0.0, +0.0) for n/2 < k < n;  with n == 2 there is no
+ *   doubled bin,
+ *   out = the reference's fft_exec(fft_init(n, -1)) on Z: n complex words, unnormalised -- the scale
+ *   already sits in q.
+ * hsfft_resample_batched, d_in: batch rows of n reals, d_out: batch rows of m reals, K = min(n, m)/2:
+ *   Y[k] = q(S[k]) for k < K,
+ *   Y[K] = q(S[K]) where m == n;  q(0.5 * S[K]) per component where m > n;  (q(S[K].re + S[K].re),
+ *   +0.0) where m < n: the imaginary part of the folded bin is +0.0, not a copy -- the reference's
+ *   c2r reads that word --
+ *   Y[k] = (+0.0, +0.0) for K < k <= m/2,
+ *   out = the reference's fft_c2r_exec(fft_real_init(m, -1)) on Y (it reads bins 0..m/2, here at
+ *   pitch m/2+1): m reals.  This is scipy's resample(x, m); its factor m/n already sits in q.
+ * Infinite and NaN bins propagate by the IEEE rules (the reference's r2c already returns an infinite
+ * bin where S + S would overflow); 0.5 * S and q round subnormals; everything is computed for every
+ * index with no special case.  Where a NaN meets arithmetic, its payload is not part of the contract.
+ * The plans come from the convolution plan cache -- the real plan pairs of n and of m, the c2c pair
+ * of n -- so results follow the calling thread's twiddle mode, and a repeated length builds nothing.
+ * Accuracy is that of the row transforms: full on powers of two; about 1e-11 in the exact mode on
+ * lengths with factors 3, 5 or 7; in the default (reference) mode lengths such as 6 and 12 give the
+ * reference's twiddle-quirk results (hsfft_set_twiddle_mode above), which are far from the
+ * definition.  The bit-exact contract holds at every even length regardless.  Bluestein inner
+ * lengths keep the error-word contract of hsfft_exec_batched (below).
+ * Alignment: the row transforms read d_in and write d_out directly, in 16-byte words, as
+ * hsfft_r2c_batched_compact, hsfft_exec_batched and hsfft_c2r_batched do with their buffers (a real
+ * row is read and written as n/2 complex words).  d_in and d_out must therefore be 16-byte aligned,
+ * as every hsfft_malloc'd pointer is; rows are n x 8, n x 16 or m x 8 bytes with n and m even, so
+ * every row then is.  A pointer that is not is rejected; there is no 8-byte path.
+ * Asynchronous on the library stream under the device lock; the input is never written; every
+ * output word is written exactly once.  Returns 0 on success and for batch == 0.  HSFFT_ERR_ARG
+ * with a message -- before any device is touched -- for NULL pointers, batch < 0, n or m odd, below 2
+ * or above 2^30, n x batch or m x batch above 2^40, a d_in or d_out that is not 16-byte aligned, or
+ * input and output byte ranges that overlap at all (each with its own element size).
+ * Scratch: the two pool buffers of hsfft_dct_batched, no allocation per call: the compact spectra,
+ * and the edited spectra that the inverse transform reads.  Rows are walked in chunks of
+ * HSFFT_SPECTRAL_CHUNK_MB / (16 x (n/2+1) + 16 x n) rows for hsfft_hilbert_batched and
+ * HSFFT_SPECTRAL_CHUNK_MB / (16 x (n/2+1) + 16 x (m/2+1)) rows for hsfft_resample_batched
+ * (HSFFT_SPECTRAL_CHUNK_MB: default 1024 MiB, at least 1, read per call), at least one and at most
+ * the batch, halved while the allocation fails; HSFFT_ERR_NOMEM if one row still fails. */
+int hsfft_hilbert_batched(const fft_type *d_in, fft_data *d_out, int n, int batch);
+int hsfft_resample_batched(const fft_type *d_in, int n, fft_type *d_out, int m, int batch);
+/* Host only, no device touched: the rows of one chunk by the rule above, before the clamp to the
+ * batch, into *rows (NULL is skipped); m == 0 asks for hsfft_hilbert_batched.  HSFFT_ERR_ARG with a
+ * message for an n or a non-zero m that is odd, below 2 or above 2^30. */
+int hsfft_spectral_chunk_rows(int n, int m, long long *rows);
 
 /* --- synthetic data and timing (benchmark support) ------------------------------------- */
 /* x[j] = (u(2(offset+j)), u(2(offset+j)+1)), u(i) = splitmix64(seed ^ i) -> [-1, 1) */

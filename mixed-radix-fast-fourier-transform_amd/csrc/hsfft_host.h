@@ -127,6 +127,11 @@ enum {
                            * number by the same argument: the call is asynchronous, runs wholly on the
                            * library stream under the device lock and calls neither the filter, the STFT
                            * nor a cosine or sine transform, so stream order separates the users */
+    HS_SCR_SPECTRAL = 2,  /* hsfft_hilbert_batched / hsfft_resample_batched (hsfft_spectral.h): a chunk's compact
+                           * spectra S.  A fifth name for the same number by the same argument: the calls
+                           * are asynchronous, run wholly on the library stream under the device lock and
+                           * call none of the other users, so stream order separates them; the row
+                           * transforms in between use the chain, Bluestein and HS_SCR_REAL_Z classes */
     HS_SCR_BLUE_MID = 3,  /* Bluestein M-point intermediate, or the persistent launch's images */
     HS_SCR_REAL_Z = 4,    /* real transforms: the inner c2c's N/2-point rows */
     HS_SCR_STAGE_IN = 5,  /* drop-in fft_exec / fft_r2c_exec / fft_c2r_exec: staged input */
@@ -144,6 +149,10 @@ enum {
     HS_SCR_CZT_SPEC = 10, /* the chirp-z calls: a chunk's spectra, then their products with the chirp's, as
                            * hsfft_dct_batched keeps its spectra here: all users of the number run on the
                            * library stream under the device lock and never call each other */
+    HS_SCR_SPECTRAL_SPEC = 10, /* the same two calls: a chunk's edited spectra, Z (rows of n words) or Y (rows
+                           * of m/2+1), which the inverse transform reads; by the argument of
+                           * HS_SCR_CZT_SPEC.  The class holds other calls' leftovers, so every word of
+                           * Z and Y, the zero ones too, is written in every chunk */
     HS_SCR_2D = 11,       /* hsfft_exec_2d / hsfft_exec_columns / the 2D real transforms (hsfft_2d.h): the
                            * chunk between the row transforms and the transposes; a class of its own,
                            * because the row transforms in between use the chain, Bluestein and
@@ -227,6 +236,17 @@ int hs_czt_freqs(const char *who, double f0, double df);
 int hs_czt_get(int dev, int n, int m, int L, double f0, double df, int mode, hs_czt_data *out);
 void hs_czt_set_ready(int dev, int slot);
 void hs_czt_release_device(int dev);
+/* The analytic signal's and Fourier resampling's host side (hsfft_spectral.c); `hilbert` set means
+ * there is no second length and m is 0.  hs_spectral_sizes: the length rule of both calls and of
+ * hsfft_spectral_chunk_rows.  hs_spectral_rows: the rows of one chunk by the documented rule, before
+ * the clamp to the batch (valid lengths only).  hs_spectral_args: every rejection of the two entry
+ * points -- pointers, batch, lengths, totals, alignment, overlap.  0, or HSFFT_ERR_ARG with the
+ * message set; none of them touches a device. */
+#define HS_SPECTRAL_MAX_LEN HS_DCT_MAX_LEN
+#define HS_SPECTRAL_MAX_WORDS (1LL << 40) /* n x batch and m x batch: dct::MAX_WORDS */
+int hs_spectral_sizes(const char *who, int n, int m, int hilbert);
+long long hs_spectral_rows(int n, int m);
+int hs_spectral_args(const char *who, const void *d_in, int n, const void *d_out, int m, int batch, int hilbert);
 /* bytes from an environment knob given in MiB (default dflt_mb; at least 1 MiB) */
 size_t hs_env_mb(const char *name, double dflt_mb);
 

@@ -88,6 +88,9 @@ SIGNATURES = {
     "hsfft_czt_tables": (CI, [CI, CI, ctypes.c_double, ctypes.c_double, VP, VP]),
     "hsfft_czt_batched": (CI, [VP, CI, VP, CI, ctypes.c_double, ctypes.c_double, CI]),
     "hsfft_czt_real_batched": (CI, [VP, CI, VP, CI, ctypes.c_double, ctypes.c_double, CI]),
+    "hsfft_hilbert_batched": (CI, [VP, VP, CI, CI]),
+    "hsfft_resample_batched": (CI, [VP, CI, VP, CI, CI]),
+    "hsfft_spectral_chunk_rows": (CI, [CI, CI, ctypes.POINTER(ctypes.c_longlong)]),
     "hsfft_fill_complex": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_fill_real": (CI, [VP, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64]),
     "hsfft_time_batched": (CI, [VP, VP, VP, CI, CI, ctypes.POINTER(ctypes.c_float),
@@ -951,6 +954,74 @@ def zoom_fft(x, fn, m=None, fs=2.0, endpoint=False):
         raise ValueError("zoom_fft: fn is a scalar or holds two frequencies")
     d = m - 1 if endpoint else m
     return czt(x, m, f1 / fs, (f2 - f1) / (d * fs) if d else 0.0)
+
+
+def spectral_chunk_rows(n, m=0):
+    """the rows of one chunk of hilbert_batched (m == 0) or resample_batched by the documented rule,
+    HSFFT_SPECTRAL_CHUNK_MB over a row's scratch bytes, before the clamp to the batch: host only"""
+    rows = ctypes.c_longlong(0)
+    check(lib().hsfft_spectral_chunk_rows(n, m, ctypes.byref(rows)), "spectral_chunk_rows")
+    return rows.value
+
+
+def hilbert_batched(d_in, d_out, n, batch):
+    """batch real rows of n samples (n even) -> batch rows of n complex: the analytic signal x + i H[x]
+    of scipy.signal.hilbert.  Both buffers 16-byte aligned.  Results follow the thread's twiddle mode:
+    full accuracy on powers of two, about 1e-11 in the exact mode on lengths with factors 3, 5 or 7,
+    and the reference's quirk results in the default mode on lengths such as 6 and 12"""
+    return check(lib().hsfft_hilbert_batched(VP(d_in.ptr), VP(d_out.ptr), n, batch), "hilbert_batched")
+
+
+def resample_batched(d_in, n, d_out, m, batch):
+    """batch real rows of n samples -> batch real rows of m samples (both even): scipy.signal.resample(x,
+    m), the spectrum truncated or zero-extended.  Both buffers 16-byte aligned.  Accuracy and twiddle
+    mode as for hilbert_batched, by both lengths"""
+    return check(lib().hsfft_resample_batched(VP(d_in.ptr), n, VP(d_out.ptr), m, batch), "resample_batched")
+
+
+def _spectral_rows(who, x):
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim not in (1, 2):
+        raise ValueError(f"{who} needs x of one or two dimensions")
+    n = x.shape[-1]
+    if n < 2 or n % 2 or n > 1 << 30:
+        raise ValueError(f"{who}: the row length is even, at least 2 and at most 2^30")
+    return x, n
+
+
+def hilbert(x):
+    """analytic signal (scipy.signal.hilbert) of the float64 rows x, of shape (n,) or (batch, n), n even:
+    complex128 of the same shape, real part x, imaginary part its Hilbert transform.  Uploads, runs
+    hsfft_hilbert_batched and downloads.  Accuracy follows the thread's twiddle mode (hilbert_batched)"""
+    x, n = _spectral_rows("hilbert", x)
+    if x.size == 0:
+        return np.empty(x.shape, dtype=np.complex128)
+    made = []
+    try:
+        d_x = DeviceBuffer.from_array(x)
+        made.append(d_x.free)
+        d_out = DeviceBuffer(x.size * 16)
+        made.append(d_out.free)
+        hilbert_batched(d_x, d_out, n, x.size // n)
+        synchronize()
+        return d_out.to_array(np.complex128).reshape(x.shape)
+    finally:
+        for release in reversed(made):
+            release()
+
+
+def resample(x, num):
+    """Fourier resampling (scipy.signal.resample(x, num)) of the float64 rows x, of shape (n,) or (batch,
+    n), to num samples per row, n and num even: float64.  Uploads, runs hsfft_resample_batched and
+    downloads.  Accuracy follows the thread's twiddle mode (hilbert_batched)"""
+    x, n = _spectral_rows("resample", x)
+    num = int(num)
+    if num < 2 or num % 2 or num > 1 << 30:
+        raise ValueError("resample: num is even, at least 2 and at most 2^30")
+    shape = x.shape[:-1] + (num,)
+    if x.size == 0:
+        return np.empty(shape, dtype=np.float64)
+    return _device_run(lambda d_x, d_w, d_out: resample_batched(d_x, n, d_out, num, x.size // n), x, None, shape)
 
 
 def r2c_batched(rplan, d_in, d_out, batch):
