@@ -438,6 +438,78 @@ int hsfft_dct4_twiddles(int n, fft_data *h_tw);
  * a length not in the cache builds its table on the host and uploads it synchronously. */
 int hsfft_dct4_batched(int kind, const fft_type *d_in, fft_type *d_out, int n, int batch);
 
+/* --- batched type-I cosine and sine transforms (DCT-I / DST-I) of real rows and images ----- */
+/* scipy's conventions with norm=None, for rows of n reals -- the transforms of grids that include
+ * their boundary points (DCT-I, Neumann) or exclude them (DST-I, Dirichlet):
+ *   DCT-I, n >= 2   X[k] = x[0] + (-1)^k x[n-1] + 2 sum_{j=1..n-2} x[j] cos(pi j k / (n-1))
+ *   DST-I, n >= 1   X[k] = 2 sum_{j=0..n-1} x[j] sin(pi (j+1) (k+1) / (n+1))
+ * Each is its own inverse up to the factor 2(n-1) (DCT-I) or 2(n+1) (DST-I).  Each is the unchanged
+ * r2c row transform of the symmetrically extended row -- length L = 2(n-1) or 2(n+1) -- with one new
+ * kernel before it and one after, neither of which does arithmetic; nothing is fused into a
+ * transform pass and there is no table.  L is even for every n, so these calls take every length,
+ * odd ones included; types 2, 3 and 4 stay even-only.  Entry points of their own: hsfft_dct_batched
+ * and hsfft_dct_2d_batched keep rejecting type 1.  An (n-1)-point fast algorithm and orthonormal
+ * scaling are out of scope.
+ * Host only, no device touched: the extended length into *L and its L/2+1 compact bins into *bins
+ * (NULL is skipped).  Returns 0, or HSFFT_ERR_ARG with a message for exactly the kinds and lengths
+ * that hsfft_dct1_batched rejects: a kind other than 0 or 1, n < 2 (cosine) or n < 1 (sine), or
+ * L > 2^30. */
+int hsfft_dct1_shape(int kind, int n, int *L, int *bins);
+/* kind: HSFFT_KIND_COS / HSFFT_KIND_SIN; d_in, d_out: batch contiguous rows of n reals.  The
+ * contract is compositional and bit-exact.  Per row x, with f = fft_real_init(L, 1):
+ * cosine, L = 2(n-1):
+ *   e[t] = x[t] for 0 <= t <= n-1, e[L-t] = x[t] for 1 <= t <= n-2,
+ *   S = bins 0..L/2 of the reference's fft_r2c_exec(f) on e -- the words hsfft_r2c_batched_compact
+ *       writes,
+ *   out[k] = S[k].re for 0 <= k <= n-1: a copy.
+ * sine, L = 2(n+1):
+ *   e[0] = e[n+1] = +0.0, e[j+1] = x[j], e[L-1-j] = x[j] with its sign bit flipped (of zeros and NaNs
+ *       too, no arithmetic) for 0 <= j <= n-1,
+ *   S as above,
+ *   out[k] = S[k+1].im with its sign bit flipped for 0 <= k <= n-1; S[0] and S[n+1] are not read.
+ * Every output word is the named component of the reference's r2c of the extended row, so results
+ * follow the calling thread's twiddle mode (the plan comes from the convolution plan cache; a
+ * repeated length builds nothing): full accuracy where L is a power of two -- n = 2^p + 1 for the
+ * cosine, n = 2^p - 1 for the sine -- about 1e-11 in the exact mode on L with factors 3, 5 or 7, and
+ * in the default (reference) mode the reference's twiddle-quirk results on L such as 6 and 12
+ * (hsfft_set_twiddle_mode above), which are far from the definition.  The bit-exact contract holds
+ * at every length regardless.  Any L a real plan supports (mixed-radix or Bluestein inner lengths,
+ * L == 2); Bluestein inner lengths keep the error-word contract of hsfft_exec_batched (below).
+ * Asynchronous on the library stream under the device lock; the input is never written; every
+ * output word is written exactly once and none is read; caller rows need the alignment of a
+ * double only (rows of odd n alternate between 8- and 16-byte alignment anyway).  Returns 0 on
+ * success and for batch == 0.  HSFFT_ERR_ARG with a message -- before any device is touched -- for a
+ * kind other than 0 or 1, n < 2 (cosine) or n < 1 (sine), L > 2^30, batch < 0, n x batch > 2^40, NULL
+ * pointers, d_in == d_out or input and output byte ranges that overlap.
+ * Scratch: the two pool buffers of hsfft_dct_batched, no allocation per call: the extended rows and
+ * their compact spectra.  Rows are walked in chunks of HSFFT_DCT_CHUNK_MB / (L x 8 + (L/2+1) x 16)
+ * rows (HSFFT_DCT_CHUNK_MB: default 1024 MiB, at least 1, read per call), at least one and at most
+ * the batch, halved while the allocation fails; HSFFT_ERR_NOMEM if one row still fails. */
+int hsfft_dct1_batched(int kind, const fft_type *d_in, fft_type *d_out, int n, int batch);
+/* batch contiguous row-major real images of n0 rows by n1 columns -> batch images of the same
+ * shape.  kind1 is the transform along the rows (axis 1, length n1), kind0 the transform along the
+ * columns (axis 0, length n0): scipy's dctn / dstn with type=1, norm=None for equal kinds; mixed
+ * kinds are what a Poisson solver on a vertex grid with mixed boundaries needs.  Applied twice it
+ * gives the image times the product of the two axes' factors.
+ * The contract is compositional and bit-exact: the result is, word for word, hsfft_dct1_batched(kind1)
+ * on every row and then hsfft_dct1_batched(kind0) on every column of that result.  The row
+ * transforms are that call's kernels unchanged; in between the images are transposed by the copy of
+ * hsfft_transpose_real_batched.  Per chunk: rows d_in -> scratch, transpose scratch -> d_out, rows
+ * d_out -> scratch (the columns, now contiguous), transpose scratch -> d_out.
+ * Everything else is hsfft_dct1_batched's, per axis: the length rule (either axis may be odd, and so
+ * may n0 x n1), the twiddle mode, the alignment of a double, asynchronous on the library stream
+ * under the device lock, d_in never written, every output word written.  Returns 0 on success and
+ * for batch == 0.  HSFFT_ERR_ARG with a message -- before any device is touched -- for a kind other
+ * than 0 or 1, an axis below 2 (cosine) or 1 (sine) or with L > 2^30, batch < 0, n0 x n1 x batch >
+ * 2^40, NULL pointers, d_in == d_out or input and output byte ranges that overlap.
+ * Scratch: one copy of a chunk in the 2D transforms' pool buffer, beside the two buffers the row
+ * transforms keep (and walk in chunks of their own, HSFFT_DCT_CHUNK_MB).  A call walks its batch in
+ * chunks of HSFFT_2D_CHUNK_MB / (16 x ceil(n0 x n1 / 2)) images (default 1024 MiB; the pool counts
+ * 16-byte words, so an odd image is rounded up by one double), at least one, at most the batch and
+ * at most what keeps a chunk's row count -- images x max(n0, n1) -- an int; halved while the
+ * allocation fails; the last chunk may be ragged. */
+int hsfft_dct1_2d_batched(int kind0, int kind1, const fft_type *d_in, fft_type *d_out, int n0, int n1, int batch);
+
 /* --- batched MDCT and IMDCT of real rows -------------------------------------------------- */
 /* The lapped transform of audio codecs: frames of 2N samples, N apart (N even, 2 to 2^30), N
  * coefficients per frame; a window d_w of 2N reals, or NULL for none.

@@ -1545,3 +1545,4 @@ int hsd_pass_timer_read(int n, float *ms)
 #include "hsfft_dct4.h"
 #include "hsfft_czt.h"
 #include "hsfft_spectral.h"
+#include "hsfft_dct1.h"

@@ -247,6 +247,20 @@ void hs_czt_release_device(int dev);
 int hs_spectral_sizes(const char *who, int n, int m, int hilbert);
 long long hs_spectral_rows(int n, int m);
 int hs_spectral_args(const char *who, const void *d_in, int n, const void *d_out, int m, int batch, int hilbert);
+/* The type-I cosine and sine transforms' host side (hsfft_dct1.c).  hs_dct1_sizes: the kind and
+ * length rule of every type-I entry point, and the extended length L = 2(n-1) or 2(n+1) (L may be
+ * NULL).  hs_dct1_rows: the rows of one chunk by the documented rule, before the clamp to the batch.
+ * hs_dct1_args, hs_dct1_args_2d: every rejection of hsfft_dct1_batched and hsfft_dct1_2d_batched.  0,
+ * or HSFFT_ERR_ARG with the message set; none of them touches a device.  The driver (hsfft_dct1.h)
+ * keeps a chunk's extended rows in HS_SCR_DCT and their compact spectra in HS_SCR_DCT_SPEC, by the
+ * argument of hsfft_dct_batched, which it never calls; hsfft_dct1_2d_batched keeps its chunk of
+ * images in HS_SCR_2D as hsfft_dct_2d_batched does. */
+#define HS_DCT1_MAX_WORDS (1LL << 40) /* n x batch, n0 x n1 x batch: dct::MAX_WORDS */
+int hs_dct1_sizes(const char *who, int kind, int n, int *L);
+long long hs_dct1_rows(int L);
+int hs_dct1_args(const char *who, int kind, const void *d_in, const void *d_out, int n, int batch, int *L);
+int hs_dct1_args_2d(const char *who, int kind0, int kind1, const void *d_in, const void *d_out, int n0, int n1, int batch,
+                    int *L0, int *L1);
 /* bytes from an environment knob given in MiB (default dflt_mb; at least 1 MiB) */
 size_t hs_env_mb(const char *name, double dflt_mb);
 

@@ -81,6 +81,9 @@ SIGNATURES = {
     "hsfft_dct_2d_batched": (CI, [CI, CI, CI, VP, VP, CI, CI, CI]),
     "hsfft_dct4_twiddles": (CI, [CI, VP]),
     "hsfft_dct4_batched": (CI, [CI, VP, VP, CI, CI]),
+    "hsfft_dct1_shape": (CI, [CI, CI, ctypes.POINTER(CI), ctypes.POINTER(CI)]),
+    "hsfft_dct1_batched": (CI, [CI, VP, VP, CI, CI]),
+    "hsfft_dct1_2d_batched": (CI, [CI, CI, VP, VP, CI, CI, CI]),
     "hsfft_mdct_shape": (CI, [CI, CI, CI, ctypes.POINTER(CI), ctypes.POINTER(CI)]),
     "hsfft_mdct_batched": (CI, [VP, CI, VP, CI, CI, VP, CI]),
     "hsfft_imdct_batched": (CI, [VP, CI, VP, CI, CI, VP, CI, CI]),
@@ -831,6 +834,106 @@ def dct4(x):
 def dst4(x):
     """DST-IV (scipy.fft.dst(x, type=4), norm=None) of the float64 rows x, of shape (n,) or (batch, n)"""
     return _dct4_run("dst4", KIND_SIN, x)
+
+
+def dct1_shape(kind, n):
+    """(L, bins) of hsfft_dct1_batched: the extended length 2(n-1) (KIND_COS) or 2(n+1) (KIND_SIN) and
+    its L/2+1 compact bins; sizes only, no device touched"""
+    v = [CI(0) for _ in range(2)]
+    check(lib().hsfft_dct1_shape(kind, n, *(ctypes.byref(x) for x in v)), "dct1_shape")
+    return tuple(x.value for x in v)
+
+
+def dct1_batched(kind, d_in, d_out, n, batch):
+    """batch real rows of n samples -> batch rows of n: DCT-I (KIND_COS, n >= 2) or DST-I (KIND_SIN,
+    n >= 1), scipy's conventions with norm=None; every length, odd ones included"""
+    return check(lib().hsfft_dct1_batched(kind, VP(d_in.ptr), VP(d_out.ptr), n, batch), "dct1_batched")
+
+
+def dct1_2d_batched(kind0, kind1, d_in, d_out, n0, n1, batch):
+    """batch real images of n0 x n1 -> batch images of n0 x n1: type I of kind1 along the rows, then of
+    kind0 along the columns (KIND_COS / KIND_SIN each), scipy's conventions with norm=None"""
+    return check(lib().hsfft_dct1_2d_batched(kind0, kind1, VP(d_in.ptr), VP(d_out.ptr), n0, n1, batch), "dct1_2d_batched")
+
+
+def _dct1_factor(kind, n):
+    """T(T(x)) = factor x: 2(n-1) for DCT-I, 2(n+1) for DST-I"""
+    return 2.0 * (n + 1) if kind == KIND_SIN else 2.0 * (n - 1)
+
+
+def _dct1_run(who, kind, x, inverse):
+    """check the shape, upload x, run hsfft_dct1_batched and download; inverse: the same transform,
+    then one division by 2.0 * (n-1) or 2.0 * (n+1) per word"""
+    x = np.asarray(x, dtype=np.float64)  # a scalar keeps its zero dimensions here and is rejected
+    if x.ndim not in (1, 2):
+        raise ValueError(f"{who} needs x of one or two dimensions")
+    x = np.ascontiguousarray(x)
+    n = x.shape[-1]
+    if n < (1 if kind == KIND_SIN else 2):
+        raise ValueError(f"{who}: the row length is at least {1 if kind == KIND_SIN else 2}")
+    if x.size == 0:
+        return np.empty(x.shape, dtype=np.float64)
+    y = _device_run(lambda d_x, d_w, d_out: dct1_batched(kind, d_x, d_out, n, x.size // n), x, None, x.shape)
+    return y / _dct1_factor(kind, n) if inverse else y
+
+
+def dct1(x):
+    """DCT-I (scipy.fft.dct(x, type=1), norm=None) of the float64 rows x, of shape (n,) or (batch, n),
+    n >= 2, odd or even: uploads, runs hsfft_dct1_batched and downloads"""
+    return _dct1_run("dct1", KIND_COS, x, False)
+
+
+def dst1(x):
+    """DST-I (scipy.fft.dst(x, type=1), norm=None) of the float64 rows x, of shape (n,) or (batch, n), n >= 1"""
+    return _dct1_run("dst1", KIND_SIN, x, False)
+
+
+def idct1(x):
+    """inverse of dct1: dct1 divided by 2.0 * (n-1) in numpy (scipy.fft.idct(x, type=1), norm=None)"""
+    return _dct1_run("idct1", KIND_COS, x, True)
+
+
+def idst1(x):
+    """inverse of dst1: dst1 divided by 2.0 * (n+1) in numpy (scipy.fft.idst(x, type=1), norm=None)"""
+    return _dct1_run("idst1", KIND_SIN, x, True)
+
+
+def _dct1n_run(who, kind, x, inverse):
+    """check the shape, upload x, run hsfft_dct1_2d_batched with `kind` on both axes and download;
+    inverse: the same transform, then one division by the product of the two axes' factors per word"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim < 2:
+        raise ValueError(f"{who} needs an array of at least two dimensions")
+    n0, n1 = x.shape[-2:]
+    least = 1 if kind == KIND_SIN else 2
+    if n0 < least or n1 < least:
+        raise ValueError(f"{who}: the last two axes are at least {least} long")
+    if x.size == 0:
+        return np.empty(x.shape, dtype=np.float64)
+    y = _device_run(lambda d_x, d_w, d_out: dct1_2d_batched(kind, kind, d_x, d_out, n0, n1, x.size // (n0 * n1)), x, None,
+                    x.shape)
+    return y / (_dct1_factor(kind, n0) * _dct1_factor(kind, n1)) if inverse else y
+
+
+def dct1n(x):
+    """2D DCT-I (scipy.fft.dctn(x, type=1), norm=None) over the last two axes of a float64 array of
+    shape (..., n0, n1), both >= 2: uploads, runs hsfft_dct1_2d_batched and downloads"""
+    return _dct1n_run("dct1n", KIND_COS, x, False)
+
+
+def dst1n(x):
+    """2D DST-I (scipy.fft.dstn(x, type=1), norm=None) over the last two axes of a float64 array"""
+    return _dct1n_run("dst1n", KIND_SIN, x, False)
+
+
+def idct1n(x):
+    """inverse of dct1n: dct1n divided by 2.0 * (n0-1) * (2.0 * (n1-1)) in numpy"""
+    return _dct1n_run("idct1n", KIND_COS, x, True)
+
+
+def idst1n(x):
+    """inverse of dst1n: dst1n divided by 2.0 * (n0+1) * (2.0 * (n1+1)) in numpy"""
+    return _dct1n_run("idst1n", KIND_SIN, x, True)
 
 
 def mdct(x, N, window=None, pad=False):
